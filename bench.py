@@ -20,7 +20,12 @@ resident); ``--workload e2e512`` is configs[4]: each rank's rows as JPEG files i
 directory -> pinned slots -> H2D -> decode + resize 512 -> D2H into pinned host memory, two batches
 in flight, reported next to the device-resident rate of the same rows (``device_resident_value``).
 
-Prints ONE JSON line (rank 0).  ``roofline`` prices the dominant kernel: algorithmic bytes per
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ``--steps`` steps and prints the
+line (``value``, ``ms_per_step``, the configuration; ``host_s`` = wall seconds of each phase outside the
+steps); ``--dump-outputs DIR`` also writes what the last timed step returned (see dump_outputs).  Everything
+else -- the pixel check, the single-lane roofline pass, the CPU baseline, configs[4]'s device-resident
+rate -- runs only with ``--full`` (``roofline``, ``stage_ms_per_step_single_lane``, ``pixel_check`` and
+``cpu_baseline`` are null without it).  ``roofline`` prices the dominant kernel: algorithmic bytes per
 launch (compressed bytes in + output bytes out) / that kernel's mean duration,
 measured with HIP events on its launch stream in a single-lane pass after the timed region (one
 dispatch per kernel per batch, nothing overlapping it; rocprofv3 summaries under profiles/).
@@ -332,6 +337,36 @@ def verify_rows(eng, blob, d_offs, d_lens, out, status, flips, rows_ext, period,
     return res_d
 
 
+# ---------------------------------------------------------------- --dump-outputs
+def dump_outputs(dirname: str, out, status, row_ids: np.ndarray, rank: int, world: int, order=None,
+                 budget: int = 48 << 20) -> dict:
+    """Writes what the last timed step handed to its caller, as float32 / float64 .npy files in `dirname`:
+
+    out.npy       the output rows (float32, the values of the uint8 / float32 tensor): every row of the batch
+                  if they fit in `budget` bytes, else a fixed sample of them (default_rng(0), the same rows on
+                  every run with the same arguments), in ascending position
+    out_rows.npy  the rank's row index of each row of out.npy (float64)
+    status.npy    the per-sample status of every row of the batch (float32)
+
+    `order` (configs[4], whose batches are in the downloader's completion order): a permutation that puts the
+    batch in row-index order first.  With several ranks every rank writes its own files (``_rank<r>`` suffix)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = int(out.shape[0])
+    keep = max(1, min(n, budget // (4 * int(out[0].numel()))))
+    pos = np.sort(np.random.default_rng(0).choice(n, keep, replace=False)) if keep < n else np.arange(n)
+    order = np.arange(n) if order is None else np.asarray(order)
+    sel = order[pos]
+    sfx = f"_rank{rank}" if world > 1 else ""
+    rows = out[torch.from_numpy(sel).to(out.device)].to(torch.float32).cpu().numpy()
+    st = torch.as_tensor(status).cpu().numpy()[order].astype(np.float32)
+    files = {"out": rows, "out_rows": np.asarray(row_ids)[sel].astype(np.float64), "status": st}
+    for name, a in files.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+    return {"dir": dirname, "files": sorted(f"{k}{sfx}.npy" for k in files), "rows": int(keep), "of": n,
+            "bytes": int(sum(a.nbytes for a in files.values()))}
+
+
 # ---------------------------------------------------------------- multi-rank launcher
 def _free_port() -> int:
     s = socket.socket()
@@ -400,6 +435,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the pixel check, the single-lane "
+                         "roofline pass, the CPU baseline (and configs[4]'s device-resident rate)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (out, status) as DIR/<name>.npy "
+                         "(float32; a fixed sample of the rows when they exceed 48 MiB)")
     ap.add_argument("--workload", choices=["vga256", "mixed512", "e2e512"], default="vga256",
                     help="vga256 = configs[1] (the headline metric); mixed512 = configs[2]: VGA..4K -> centre crop + "
                          "resize 512 + hflip(p=0.5) + CHW float normalise")
@@ -417,6 +458,8 @@ def main():
                     help="configs[4]: threads of the restated ParallelDownloader (the reference's num_downloading_workers "
                          "default, dataset.py:61; 4 / 8 / 16 threads: 53-56k / 49-57k / 44-50k images/s warm and "
                          "10.0-10.3k / 5.8-8.3k / 5.5-6.7k cold, profiles/r06_e2e_dl_workers.txt)")
+    # (--cpu-*, --no-cpu-baseline, --roofline-steps, --profile-steps and --no-pixel-check shape what --full
+    # adds; a plain run ignores them)
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
     ap.add_argument("--cpu-files", type=int, default=1000, help="files in the CPU-baseline folder (configs[0])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -431,6 +474,18 @@ def main():
                     help="experiments only (timing of deliberately wrong kernel variants): skip the pixel check; the "
                          "line then carries pixel_check null")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    t_start = time.perf_counter()
+    host_s = {}  # wall seconds per phase outside the steps
+
+    def phase(name):
+        nonlocal t_start
+        t = time.perf_counter()
+        host_s[name] = round(t - t_start, 3)
+        t_start = t
+
+    full = args.full
     mixed = args.workload == "mixed512"
     e2e = args.workload == "e2e512"
     # batches: one engine call per step, whose lanes drain at its end (the caller's stream orders the
@@ -456,6 +511,7 @@ def main():
     import torch
     import torch.distributed as dist
 
+    phase("import_torch")
     stub = args.engine == "stub"
     rank, world, local_rank = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), \
         int(os.environ.get("LOCAL_RANK", 0))
@@ -495,6 +551,7 @@ def main():
 
     workers = max(1, cpu_share()[0] // max(1, world))
     pool = make_pool(args.pool, workers, _make_mixed_image if mixed else _make_pool_image)
+    phase("encode_pool")
 
     # The sample index: a synthetic parquet file (sds's index layout, sds_amd/index.py) of
     # total_rows rows, row i referring to pool image i % POOL, written once by rank 0; each rank reads
@@ -553,6 +610,7 @@ def main():
     d_lens = torch.from_numpy(lens.astype(np.int32)).to(dev)
     del d_tmpl
     sync()
+    phase("index_and_upload")
 
     if stub:
         eng = StubEngine()
@@ -623,7 +681,8 @@ def main():
         # every blocking stream).  The device still serialises each D2H (a 15.0 ms blit kernel per
         # 1,024 rows) with the next batch's 3.1 ms decode: profiles/r06_e2e_trace.txt
         work = torch.cuda.Stream(dev)
-        pipe = {"k": 0, "prev": None, "bad": 0, "done": 0, "taken": 0, "keys": [None, None], "last": None}
+        pipe = {"k": 0, "prev": None, "bad": 0, "done": 0, "taken": 0, "keys": [None, None], "last": None,
+                "last_status": None}
 
         def complete_prev():
             prev = pipe["prev"]
@@ -633,7 +692,7 @@ def main():
             if not zero_copy:
                 with torch.cuda.stream(d2h):
                     hosts[prev].copy_(o, non_blocking=True)
-            pipe["prev"], pipe["last"] = None, prev
+            pipe["prev"], pipe["last"], pipe["last_status"] = None, prev, st
 
         # host wall time per phase of the step (seconds, summed; reset with the timed region): scheduling the
         # downloads ahead, taking the batch's completed rows from the downloader, engine.submit (file reads
@@ -697,6 +756,7 @@ def main():
     n_bad = pipe["bad"] if e2e else int((status != 0).sum().item())
     if n_bad:
         raise SystemExit(f"rank {rank}: {n_bad} samples failed to decode")
+    phase("engine_and_first_step")
     for _ in range(args.warmup):
         step()
 
@@ -742,7 +802,15 @@ def main():
     value = imgs / elapsed
     step = dev_step  # the pixel check and the roofline run the device-resident path on the same rows
     dev_value = None
-    if e2e:  # configs[4] asks for the rate next to the device-resident one: same rows, batch, output
+    dumped = None
+    if args.dump_outputs:  # (before anything below runs the engine again: `out` still holds the last timed batch)
+        if e2e:
+            keys = np.asarray(pipe["keys"][pipe["last"]]) - r0
+            dumped = dump_outputs(args.dump_outputs, hosts[pipe["last"]], pipe["last_status"], keys, rank, world,
+                                  order=np.argsort(keys, kind="stable"))
+        else:
+            dumped = dump_outputs(args.dump_outputs, out, status, (last_start + np.arange(B)) % nrows, rank, world)
+    if e2e and full:  # configs[4] asks for the rate next to the device-resident one: same rows, batch, output
         for _ in range(args.warmup):
             step()
         barrier()
@@ -758,7 +826,7 @@ def main():
     # of its pool image -- decoded once by the engine and checked against PIL (the reference's arithmetic)
     # on the host -- plus, for configs[1], pool image 0 against the reference-generated golden digest
     pixel_check = None
-    if not stub and not args.no_pixel_check:
+    if full and not stub and not args.no_pixel_check:
         pixel_check = verify_rows(eng, blob, d_offs, d_lens, out, status, flips, j, period, pool, nrows, B,
                                   args.res, mixed, None if e2e else last_start, dev_step, cursor, cpu_share()[0],
                                   e2e_last=(hosts[pipe["last"]], np.asarray(pipe["keys"][pipe["last"]]) - r0)
@@ -776,31 +844,47 @@ def main():
         if not pixel_check["equal_to_pil"] or not pixel_check.get("golden_sha256_match", True):
             raise SystemExit(f"rank {rank}: pixel check failed: {pixel_check}")
 
-    # roofline: every kernel timed alone in a single-lane pass (one dispatch per kernel per batch)
-    eng.set_lanes(1)
-    eng.set_timing(True)
-    for _ in range(args.roofline_steps):
-        step()
-    stages = eng.stage_times()  # summed device ms per stage over the roofline steps
-    eng.set_timing(False)
-    eng.set_lanes(4)
-    sync()
-
     mean_in = float(np.mean(t_lens))
-    out_bytes = 3 * args.res * args.res * (4 if mixed else 1)
-    alg_bytes_per_img = mean_in + out_bytes
-    dom = max(stages, key=stages.get)
-    launch_ms = stages[dom] / args.roofline_steps
-    launch_bytes = B * alg_bytes_per_img
-    achieved = launch_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
-    pmc_path = PMC_JSONS["mixed512" if mixed else "vga256"]
-    traffic = pmc_traffic(dom, B, 1, pmc_path)
-    if args.profile_steps and rank == 0:
-        print(json.dumps({"stage_ms_per_step_single_lane": {k: v / args.roofline_steps for k, v in stages.items()}}),
-              file=sys.stderr)
+    roofline = stages = None
+    if full:
+        # roofline: every kernel timed alone in a single-lane pass (one dispatch per kernel per batch)
+        eng.set_lanes(1)
+        eng.set_timing(True)
+        for _ in range(args.roofline_steps):
+            step()
+        stages = eng.stage_times()  # summed device ms per stage over the roofline steps
+        eng.set_timing(False)
+        eng.set_lanes(4)
+        sync()
+
+        out_bytes = 3 * args.res * args.res * (4 if mixed else 1)
+        alg_bytes_per_img = mean_in + out_bytes
+        dom = max(stages, key=stages.get)
+        launch_ms = stages[dom] / args.roofline_steps
+        launch_bytes = B * alg_bytes_per_img
+        achieved = launch_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+        pmc_path = PMC_JSONS["mixed512" if mixed else "vga256"]
+        traffic = pmc_traffic(dom, B, 1, pmc_path)
+        if args.profile_steps and rank == 0:
+            print(json.dumps({"stage_ms_per_step_single_lane":
+                              {k: v / args.roofline_steps for k, v in stages.items()}}), file=sys.stderr)
+        # bound: of the schema's roofs (HBM, MFMA) the path can only be priced against HBM -- it issues
+        # no MFMA; `limiter` says from the counters which roof (HBM bytes or VALU issue) it is nearest
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                    "traffic": (traffic or {}).get("bytes_per_launch"),
+                    "traffic_detail": traffic,
+                    "algorithmic_bytes_per_launch": round(launch_bytes),
+                    "algorithmic_bytes_per_image": round(alg_bytes_per_img, 1),
+                    "launch_ms": round(launch_ms, 4), "images_per_launch": B, "lanes": 1,
+                    "timing": "HIP events on the launch stream, single-lane pass after the timed region",
+                    "limiter": measured_limiter(dom, B, launch_ms, traffic, pmc_path),
+                    "pipeline_achieved": round(value / world * alg_bytes_per_img / 1e9, 2)}
+        if e2e:
+            roofline["note"] = "device-resident kernels of the same rows (the PCIe legs are not kernels)"
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and not stub:
         procs, procs_src = cpu_share()
         folder = tempfile.mkdtemp(prefix="sdsj_cpu_")
         try:
@@ -860,30 +944,21 @@ def main():
             "process_group": {"backend": dist.get_backend() if use_pg else None, "world_size": world_seen,
                               "gpus_visible": ndev if not stub else 0, "forced_at_world_size_1": bool(args.force_pg),
                               "all_gather_device": gather_dev},
-            # bound: of the schema's roofs (HBM, MFMA) the path can only be priced against HBM -- it issues
-            # no MFMA; `limiter` says from the counters which roof (HBM bytes or VALU issue) it is nearest
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": (traffic or {}).get("bytes_per_launch"),
-                         "traffic_detail": traffic,
-                         "algorithmic_bytes_per_launch": round(launch_bytes),
-                         "algorithmic_bytes_per_image": round(alg_bytes_per_img, 1),
-                         "launch_ms": round(launch_ms, 4), "images_per_launch": B, "lanes": 1,
-                         "timing": "HIP events on the launch stream, single-lane pass after the timed region",
-                         "limiter": measured_limiter(dom, B, launch_ms, traffic, pmc_path),
-                         "pipeline_achieved": round(value / world * alg_bytes_per_img / 1e9, 2)},
-            "stage_ms_per_step_single_lane": {k: round(v / args.roofline_steps, 4) for k, v in stages.items()},
+            "full": full, "host_s": host_s, "outputs_dumped": dumped,
+            # the keys from here on are measured by --full only (null in a plain run)
+            "roofline": roofline,
+            "stage_ms_per_step_single_lane": stages and {k: round(v / args.roofline_steps, 4)
+                                                         for k, v in stages.items()},
             "pixel_check": pixel_check,
             "cpu_baseline": cpu,
         }
         if e2e:
-            line["device_resident_value"] = round(dev_value, 1)
-            line["e2e_over_device_resident"] = round(value / dev_value, 4)
+            line["device_resident_value"] = dev_value and round(dev_value, 1)
+            line["e2e_over_device_resident"] = dev_value and round(value / dev_value, 4)
             line["downloader"] = dl_rates
             line["e2e_out"] = args.e2e_out
             line["e2e_host_ms_per_step"] = {k: round(v / args.steps * 1e3, 3) for k, v in ph.items()}
             line["e2e_host_ms_per_step"]["step"] = round(elapsed / args.steps * 1e3, 3)
-            line["roofline"]["note"] = "device-resident kernels of the same rows (the PCIe legs are not kernels)"
         print(json.dumps(line), file=result_out, flush=True)
     if use_pg:
         dist.barrier()

@@ -16,7 +16,8 @@ arithmetic therefore comes from Pillow 12.2.0 + libjpeg-turbo 3.1.4 exactly as i
 reference's deployment.  Bytecode writing is disabled so nothing lands in /root/reference.
 
 Outputs (all data, no reference source):
-  g1_small.npz      G1: small JPEG bytes, decoded RGB, pipeline outputs at 3 resolutions
+  g1_small.<k>.npz  G1: small JPEG bytes, decoded RGB, pipeline outputs at 3 resolutions (parts under 1 MiB,
+                    tests/goldens.py save_npz / load_npz)
   g1_cases.json     G1: per-case parameters + reference outcome (ok / exception type)
   g2_synth.json     G2: 8 synthetic 640x480 q90 (bench generator) digests at 256x256
   g2_full0.npy      G2: one full 256x256 uint8 CHW output
@@ -197,7 +198,8 @@ def main():
                 outs[key] = {"status": type(e).__name__}
         case["outputs"] = outs
         cases.append(case)
-    np.savez_compressed(os.path.join(HERE, "g1_small.npz"), **arrays)
+    from tests import goldens
+    goldens.save_npz("g1_small", arrays)
     with open(os.path.join(HERE, "g1_cases.json"), "w") as f:
         json.dump(cases, f, indent=1)
 

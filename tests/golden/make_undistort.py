@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates G8 (tests/golden/g8_undistort.npz + .json): the reference's UndistortFramesTransform
+"""Generates G8 (tests/golden/g8_undistort.<k>.npz + .json): the reference's UndistortFramesTransform
 (sds/transforms/presets.py:164-188), alone and followed by ResizeVideoTransform +
 ConvertVideoToByteTensorTransform (presets.py:121-135), on PIL frames.
 
@@ -83,7 +83,8 @@ def main():
         entry.update(ok=True, video_shape=list(v.shape), video_dtype=str(v.dtype).replace("torch.", ""))
         cases.append(entry)
 
-    np.savez_compressed(os.path.join(HERE, "g8_undistort.npz"), **arrays)
+    from tests import goldens
+    goldens.save_npz("g8_undistort", arrays)
     with open(os.path.join(HERE, "g8_undistort.json"), "w") as f:
         json.dump({"generator": "tests/golden/make_undistort.py (reference presets.py UndistortFramesTransform, "
                                 "ResizeVideoTransform, ConvertVideoToByteTensorTransform, unmodified, with "

@@ -95,14 +95,13 @@ def test_undistort_then_video_resize_matches_the_reference_fixture():
     frames (tests/golden/make_undistort.py) -- including the key routing and the skip / same-size cases."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    import os
 
     from PIL import Image
 
     from sds_amd.presets import GpuResizeVideoTransform, GpuUndistortFramesTransform
     from tests import goldens as G
     meta = G.load_json("g8_undistort.json")
-    z = np.load(os.path.join(G.GOLDEN, "g8_undistort.npz"))
+    z = G.load_npz("g8_undistort")
     for c in meta["cases"]:
         name = c["name"]
         fr = z[name + "__frames"]

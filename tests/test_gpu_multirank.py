@@ -22,8 +22,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_index_sharded_on_hip():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rows", "4096",
-           "--batch", "1024", "--steps", "2", "--warmup", "1", "--pool", "64", "--roofline-steps", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
+           "--rows", "4096", "--batch", "1024", "--steps", "2", "--warmup", "1", "--pool", "64", "--roofline-steps", "1",
            "--no-cpu-baseline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=REPO)
@@ -49,8 +49,8 @@ def test_bench_rccl_process_group_at_world_size_1():
     all_gather of the timed region (sds/utils/distributed.py:22-40 uses the 'nccl' backend)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-pg", "--backend", "nccl",
-           "--rows", "4096", "--batch", "1024", "--steps", "2", "--warmup", "1", "--pool", "64",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "1", "--force-pg", "--backend",
+           "nccl", "--rows", "4096", "--batch", "1024", "--steps", "2", "--warmup", "1", "--pool", "64",
            "--roofline-steps", "1", "--no-cpu-baseline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):

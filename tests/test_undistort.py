@@ -3,7 +3,6 @@ restatement of its resize (lean_resize_frames: centre crop + Pillow bilinear, fu
 drop-in's host logic (the aspect check, the skip cases, the key routing, the reference's AssertionError)
 against G8 -- fixtures made by running the reference (tests/golden/make_undistort.py).  The GPU values are
 checked in tests/test_gpu_frames.py."""
-import os
 
 import numpy as np
 import pytest
@@ -16,7 +15,7 @@ torch = pytest.importorskip("torch")
 
 def _g8():
     meta = G.load_json("g8_undistort.json")
-    z = np.load(os.path.join(G.GOLDEN, "g8_undistort.npz"))
+    z = G.load_npz("g8_undistort")
     return meta["cases"], z
 
 

@@ -5,7 +5,7 @@
 set -e
 export TMPDIR=/tmp
 rounds=$1; shift
-args=$1; shift
+args="--full $1"; shift  # (--full: the per-stage single-lane times of the log line)
 mkdir -p gpurun_out
 for r in $(seq 1 $rounds); do
   for spec in "$@"; do

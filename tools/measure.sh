@@ -16,6 +16,8 @@
 # Outputs land under gpurun_out/ (TAG_*.json / *.log); copy what is to be kept into profiles/.
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+out=${OUT:-out}  # where the bench lines (bench.py --full) go
+mkdir -p "$out"
 part=${1:-suite}
 shift || true
 case "$part" in
@@ -27,9 +29,9 @@ case "$part" in
   lines)
     tag=${1:-rNN}
     tools/gpu_steps.sh \
-      "bench|300|python bench.py > gpurun_out/${tag}_bench.json" \
-      "mixed|300|python bench.py --workload mixed512 > gpurun_out/${tag}_bench_mixed512.json" \
-      "e2e|300|python bench.py --workload e2e512 > gpurun_out/${tag}_bench_e2e512.json" \
+      "bench|300|python bench.py --full > $out/${tag}_bench.json" \
+      "mixed|300|python bench.py --full --workload mixed512 > $out/${tag}_bench_mixed512.json" \
+      "e2e|300|python bench.py --full --workload e2e512 > $out/${tag}_bench_e2e512.json" \
       "prog|300|python tools/prog_bench.py 4096 > gpurun_out/${tag}_prog_bench.json" \
       "sampling|300|python tools/sampling_bench.py 4096 > gpurun_out/${tag}_sampling.jsonl" \
       "svc|200|python tools/service_bench.py 3 1 2 4 8 16 32" \
@@ -49,7 +51,7 @@ case "$part" in
     tools/gpu_steps.sh \
       "prof|900|tools/profile_round.sh $tag" \
       "pmcmixed|600|BATCH=8192 PMC_OUT=pmc_mixed512.json tools/pmc.sh --workload mixed512" \
-      "ranks8|300|python bench.py --gpus 8 --backend gloo --batch 2048 --steps 3 --warmup 1 --no-cpu-baseline --roofline-steps 1 > gpurun_out/${tag}_rehearsal_8ranks_1gpu.json"
+      "ranks8|300|python bench.py --full --gpus 8 --backend gloo --batch 2048 --steps 3 --warmup 1 --no-cpu-baseline --roofline-steps 1 > $out/${tag}_rehearsal_8ranks_1gpu.json"
     ;;
   ab)
     tools/ab.sh "$@"

@@ -2,10 +2,10 @@
 # Entropy warm-up sweep at the bench's default batch (SDSJ_WARM_BITS overrides the plan's warm-up for
 # every image): one bench line per setting into gpurun_out/warm.log.  usage: tools/warm_sweep.sh bits... [-- bench args]
 mkdir -p gpurun_out
-args=()
+args=(--full)  # (--full: the single-lane stage times read below)
 vals=()
 while [ $# -gt 0 ]; do
-  if [ "$1" = "--" ]; then shift; args=("$@"); break; fi
+  if [ "$1" = "--" ]; then shift; args=(--full "$@"); break; fi
   vals+=("$1"); shift
 done
 for r in 1 2; do
