@@ -95,9 +95,37 @@ int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out);
  * batch on the device-resident entry point needs the sum over its samples (sdsj_engine_reserve). */
 int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* need);
 
+/* Sample formats an engine decodes natively (sdsj_engine_set_formats).  JPEG only by default; PNG is
+ * opt-in: non-interlaced, bit depth 8, colour types 0, 2, 3, 4, 6, giving the pixels of
+ * PIL.Image.open(...).convert("RGB") -- gray replicated, alpha dropped, tRNS ignored, palette indices
+ * at or beyond the PLTE length black.  A PNG outside that subset (interlaced, other depths, APNG, chunks
+ * this path does not know before the image data) reports SDSJ_UNSUPPORTED and a stream this path is
+ * not sure PIL decodes to the same pixels SDSJ_CORRUPT; callers rerun both on PIL, as for JPEG. */
+#define SDSJ_FORMAT_JPEG 1
+#define SDSJ_FORMAT_PNG 2
+
+typedef struct sdsj_png_info {
+    int32_t width, height;
+    int32_t bit_depth, color_type, interlace; /* IHDR fields */
+    int32_t supported;                        /* 1 if the MI355X path decodes it (when PNG is enabled) */
+} sdsj_png_info;
+
+/* Host-side header parse of one PNG up to its first IDAT chunk (no GPU needed): IHDR fields as soon as
+ * IHDR is readable, and the status k_parse would give the sample with SDSJ_FORMAT_PNG enabled. */
+int sdsj_png_probe(const uint8_t* png, size_t n, sdsj_png_info* out);
+
+/* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
+ * has SDSJ_FORMAT_PNG (a format outside the mask reports SDSJ_UNSUPPORTED, need 0). */
+int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need);
+
 /* Creates an engine bound to HIP device `hip_device`.  Scratch memory is owned by the engine. */
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out);
 int sdsj_engine_destroy(sdsj_engine* eng);
+
+/* Sets the formats (SDSJ_FORMAT_* mask, at least one) the engine decodes in batches submitted after the
+ * call, on every decode entry point: sdsj_decode_resize_batch, sdsj_decode_resize_batch_device,
+ * sdsj_submit_batch, sdsj_submit_files (and so what sdsj_wait_batch reports).  Default: JPEG only. */
+int sdsj_engine_set_formats(sdsj_engine* eng, int mask);
 
 /* Decode + crop + resize (+flip, +normalise) of n JPEGs held in HOST memory.
  *   jpg[i], len[i]  : encoded bytes of sample i (borrowed)
@@ -166,7 +194,8 @@ int sdsj_resize_frames_device(sdsj_engine* eng, int n, const uint8_t* d_frames, 
 #define SDSJ_CTR_BYTES_OUT 7   /* output tensor bytes written (failed samples included: zeros) */
 #define SDSJ_CTR_FRAMES 8      /* raw frames resized (sdsj_resize_frames_device) */
 #define SDSJ_CTR_PROGRESSIVE 9 /* progressive JPEGs decoded */
-#define SDSJ_NUM_COUNTERS 10
+#define SDSJ_CTR_PNG 10        /* PNG samples decoded natively (SDSJ_FORMAT_PNG) */
+#define SDSJ_NUM_COUNTERS 11
 int sdsj_engine_counters(sdsj_engine* eng, uint64_t* out, int cap, int reset);
 const char* sdsj_counter_name(int k);
 
@@ -241,7 +270,8 @@ int sdsj_service_serve(const sdsj_service_cfg* cfg);
 int sdsj_engine_debug_buffers(const sdsj_engine* eng, void** scratch, void** descs, int64_t* desc_bytes,
                               int64_t* scratch_bytes);
 
-/* Name of stage k of sdsj_engine_stage_times ("parse", "unstuff", "entropy", ...). */
+/* Name of stage k of sdsj_engine_stage_times ("parse", "unstuff", "entropy", ...; the PNG kernels'
+ * "png_inflate" and "png_unfilter" come last, though they run after "prog"). */
 const char* sdsj_stage_name(int k);
 
 #ifdef __cplusplus

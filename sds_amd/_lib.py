@@ -33,9 +33,29 @@ EXPORTS = [
     "sdsj_decode_resize_batch_device", "sdsj_engine_set_timing", "sdsj_engine_stage_times", "sdsj_last_error",
     "sdsj_stage_name", "sdsj_engine_debug_buffers", "sdsj_resize_frames_device", "sdsj_submit_batch",
     "sdsj_submit_files", "sdsj_wait_batch", "sdsj_engine_counters", "sdsj_counter_name", "sdsj_engine_set_lanes",
-    "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve",
+    "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve", "sdsj_engine_set_formats", "sdsj_png_probe",
+    "sdsj_plan_need_formats",
 ]
-NUM_COUNTERS = 10  # SDSJ_NUM_COUNTERS
+NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
+FORMAT_JPEG, FORMAT_PNG = 1, 2  # SDSJ_FORMAT_*
+FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG}
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def format_mask(formats) -> int:
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "png" (None: JPEG only, the engine's default)."""
+    if formats is None:
+        return FORMAT_JPEG
+    if isinstance(formats, str):
+        formats = (formats,)
+    mask = 0
+    for f in formats:
+        if f not in FORMATS:
+            raise ValueError(f"unknown format {f!r}: expected a tuple of {sorted(FORMATS)}")
+        mask |= FORMATS[f]
+    if not mask:
+        raise ValueError("formats must name at least one of " + ", ".join(sorted(FORMATS)))
+    return mask
 SLOTS = 2  # SDSJ_SLOTS: batches in flight on the asynchronous host path
 
 
@@ -48,6 +68,11 @@ class SdsjInfo(ctypes.Structure):
                 ("h_samp", ctypes.c_int32 * 3), ("v_samp", ctypes.c_int32 * 3),
                 ("restart_interval", ctypes.c_int32), ("supported", ctypes.c_int32),
                 ("entropy_offset", ctypes.c_int64)]
+
+
+class SdsjPngInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32),
+                ("color_type", ctypes.c_int32), ("interlace", ctypes.c_int32), ("supported", ctypes.c_int32)]
 
 
 class SdsjCfg(ctypes.Structure):
@@ -117,6 +142,10 @@ def load() -> ctypes.CDLL:
         lib.sdsj_engine_reserve.argtypes = [vp, i64]
         lib.sdsj_plan_need.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjOp), ctypes.POINTER(i64)]
         lib.sdsj_service_serve.argtypes = [ctypes.POINTER(SdsjServiceCfg)]
+        lib.sdsj_engine_set_formats.argtypes = [vp, ctypes.c_int]
+        lib.sdsj_png_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjPngInfo)]
+        lib.sdsj_plan_need_formats.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjOp), ctypes.c_int,
+                                               ctypes.POINTER(i64)]
         for name in EXPORTS:
             getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         if lib.sdsj_abi_version() != SDSJ_ABI_VERSION:
@@ -128,4 +157,10 @@ def load() -> ctypes.CDLL:
 def probe(jpg: bytes) -> tuple[int, SdsjInfo]:
     info = SdsjInfo()
     st = load().sdsj_probe(jpg, len(jpg), ctypes.byref(info))
+    return st, info
+
+
+def png_probe(png: bytes) -> tuple[int, SdsjPngInfo]:
+    info = SdsjPngInfo()
+    st = load().sdsj_png_probe(png, len(png), ctypes.byref(info))
     return st, info

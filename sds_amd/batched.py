@@ -228,12 +228,15 @@ class GpuDecodeBatch:
     ``return_image_as_single_frame_video`` mirrors presets.py:737-742 on the batch: ``video`` =
     ``[B, 1, 3, H, W]``, ``image`` removed, ``framerate`` = 960.0 per sample (float64, as
     default_collate stacks Python floats).
+    ``gpu_formats``: the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"png"``
+    (default JPEG only; see presets.GpuDecodeResizeImageTransform).  With ``"png"`` a PNG shard no longer
+    decodes one sample at a time on a host core; PNG on the GPU is meant for this batched use.
     """
 
     def __init__(self, image_field: str, resolution, output_field: str = "image", normalize: bool = False,
                  resize_kwargs: Optional[dict] = None, device=None, hflip_prob: float = 0.0,
                  on_error: str = "drop", return_image_as_single_frame_video: bool = False,
-                 video_output_field: str = "video"):
+                 video_output_field: str = "video", gpu_formats=("jpeg",)):
         self.image_field = image_field
         self.output_field = output_field
         self.resolution = tuple(int(v) for v in resolution)
@@ -250,6 +253,8 @@ class GpuDecodeBatch:
         self.hflip_prob = float(hflip_prob)
         self.as_video = bool(return_image_as_single_frame_video)
         self.video_output_field = video_output_field
+        self.gpu_formats = tuple(gpu_formats)
+        _lib.format_mask(self.gpu_formats)
 
     def _inputs(self, batch: dict):
         """The batch's encoded images and their hflip coins (one torch.rand(1) per sample, batch order)."""
@@ -267,10 +272,14 @@ class GpuDecodeBatch:
         return dict(crop_before_resize=kw.get("crop_before_resize", True),
                     filter=F.filter_name(kw.get("interpolation_mode", "bilinear")), normalize=self.normalize)
 
+    def _dec_opts(self) -> dict:
+        # (nothing added for the default: the engine call's own default is JPEG only)
+        return self._opts() if self.gpu_formats == ("jpeg",) else dict(self._opts(), formats=self.gpu_formats)
+
     def __call__(self, batch: dict) -> dict:
         encoded, flip = self._inputs(batch)
         eng = get_engine(self.device)
-        images, status = eng.decode_resize(encoded, self.resolution, flip=flip, **self._opts())
+        images, status = eng.decode_resize(encoded, self.resolution, flip=flip, **self._dec_opts())
         return self._finish(eng, batch, encoded, flip, images, status)
 
     def stream(self, batches: Iterable[dict]) -> Iterator[dict]:
@@ -293,12 +302,12 @@ class GpuDecodeBatch:
                     if pending is not None:
                         prev, pending = pending, None
                         yield self._collect(eng, prev)
-                    images, status = eng.decode_resize(encoded, self.resolution, flip=flip, **self._opts())
+                    images, status = eng.decode_resize(encoded, self.resolution, flip=flip, **self._dec_opts())
                     yield self._finish(eng, batch, encoded, flip, images, status)
                     continue
                 slot = k % _lib.SLOTS
                 k += 1
-                eng.submit(slot, encoded, self.resolution, flip=flip, **self._opts())
+                eng.submit(slot, encoded, self.resolution, flip=flip, **self._dec_opts())
                 prev, pending = pending, (slot, batch, encoded, flip)
                 batch = encoded = None  # (the consumer's reference is then the batch's last one)
                 if prev is not None:

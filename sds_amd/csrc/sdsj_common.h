@@ -220,6 +220,14 @@ struct ImgDesc {
   int8_t sm_pad[3];
   int32_t etab;  // k_enttab: the image whose EntTables it decodes with (itself, or image 0 of the lane when equal)
   int32_t etab_pad;
+  // PNG sample (sdsj_png.h png_parse; engines with SDSJ_FORMAT_PNG enabled): no components or entropy
+  // data; k_png_inflate fills the scanline buffer at off_png (png_raw bytes: height x (1 + width x
+  // png_bpp)) from the IDAT chain at png_idat_pos, k_png_unfilter writes the RGB rows at off_rgb
+  int32_t png;
+  int32_t png_ctype, png_bpp, png_plte_n;  // colour type, scanline bytes per pixel, PLTE entries
+  int64_t png_plte_pos, png_idat_pos;      // relative to the sample's first byte
+  int64_t png_raw;
+  int64_t off_png;
 };
 
 // One tile of k_unstuff's first pass: bytes it emits and split markers (RSTn, codes below SOF0) it
@@ -315,6 +323,7 @@ enum Route : int32_t {
   kRtProg,                        // progressive images (k_prog)
   kRtEnt11G,                      // (count only) (image, group) tasks of the kRtEnt11M images: group_tasks()
   kRtUsSmall, kRtUsBig,           // unstuffing: k_us_serial / the tile-parallel passes (kUsSerialTiles)
+  kRtPng,                         // PNG samples (k_png_inflate, k_png_unfilter); they resample through kRtUnfused
   kNumRoutes
 };
 constexpr int kRouteSlots = 48;  // counts [0, kNumRoutes), the rest zero

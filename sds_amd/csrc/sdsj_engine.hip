@@ -31,14 +31,19 @@
 using namespace sdsj;
 
 namespace {
-constexpr int kStages = 13;
+constexpr int kStages = 15;
 #ifndef SDSJ_MAX_LANES
 #define SDSJ_MAX_LANES 4
 #endif
 constexpr int kMaxLanes = SDSJ_MAX_LANES;
-const char* kStageNames[kStages] = {"parse", "plan",  "unstuff", "prog",  "entspec", "entsync", "entwrite",
-                                    "idct",  "color", "coeffs",  "hpass", "vpass",   "resample"};
+const char* kStageNames[kStages] = {"parse", "plan",  "unstuff", "prog",  "entspec",  "entsync",     "entwrite",    "idct",
+                                    "color", "coeffs", "hpass",   "vpass", "resample", "png_inflate", "png_unfilter"};
 constexpr int kMarkAfterSpec = 5;  // mark index at the end of the entspec stage
+// The PNG kernels run between "prog" and "entspec", but their stages are named last (stage indices are
+// part of the interface).  A lane's events are recorded in time order: stage k spans the events
+// stage_event(k) and stage_event(k) + 1.
+constexpr int kPngEvent = 4;  // events 4, 5: the starts of k_png_inflate and k_png_unfilter
+constexpr int stage_event(int k) { return k < 4 ? k : k < 13 ? k + 2 : kPngEvent + (k - 13); }
 }  // namespace
 
 struct sdsj_engine {
@@ -46,6 +51,7 @@ struct sdsj_engine {
   int max_batch = 4096;
   int64_t capacity = 0;
   bool grow = true;
+  int formats = SDSJ_FORMAT_JPEG;  // sdsj_engine_set_formats
   int warm_bits = -1;  // entropy warm-up override (SDSJ_WARM_BITS, experiments); < 0 = plan default
   uint8_t* scratch = nullptr;
   ImgDesc* descs = nullptr;
@@ -210,18 +216,19 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   std::vector<hipEvent_t>* evs = nullptr;
   if (e->timing) {
     if (e->ev_used == e->ev_sets.size()) {
-      std::vector<hipEvent_t> set(kStages + 1);
+      std::vector<hipEvent_t> set(kStages + 1);  // (in time order: stage_event)
       for (auto& ev : set) SDSJ_HIP(e, hipEventCreate(&ev));
       e->ev_sets.push_back(set);
     }
     evs = &e->ev_sets[e->ev_used++];
   }
-  auto mark = [&](int k) {
-    if (evs) (void)hipEventRecord((*evs)[k], s);
+  auto mark = [&](int k) {  // (k: the mark before stage k of the JPEG sequence, kStageNames[k])
+    if (evs) (void)hipEventRecord((*evs)[k < kPngEvent ? k : k + 2], s);
     if (after_spec && (e->lane_mid == k || (e->lane_mid < 0 && k == kMarkAfterSpec))) (void)hipEventRecord(after_spec, s);
   };
   mark(0);
-  SDSJ_HIP(e, launch_parse(n, d_blob, blob_bytes, d_offsets, d_lengths, op, e->warm_bits, small, ln.descs, ln.tables, s));
+  SDSJ_HIP(e, launch_parse(n, d_blob, blob_bytes, d_offsets, d_lengths, op, e->warm_bits, small, ln.descs, ln.tables, s,
+                           e->formats));
   mark(1);
   const int cap = e->max_batch;
   SDSJ_HIP(e, launch_plan(n, ln.descs, e->capacity, ln.base, ln.total, ln.routes, cap, s));
@@ -236,6 +243,12 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   mark(3);
   // (after mark 3: the next lane may start while this lane's progressive images decode)
   SDSJ_HIP(e, launch_prog(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch, ln.routes, cap, s, rm, hint));
+  if (evs) (void)hipEventRecord((*evs)[kPngEvent], s);
+  if (e->formats & SDSJ_FORMAT_PNG)
+    SDSJ_HIP(e, launch_png(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch, ln.routes, cap, s, rm, hint,
+                           evs ? (*evs)[kPngEvent + 1] : nullptr));
+  else if (evs)
+    (void)hipEventRecord((*evs)[kPngEvent + 1], s);
   mark(4);
   SDSJ_HIP(e, launch_entspec(n, ln.descs, ln.tables, ln.etab, e->scratch, ln.routes, cap, s, rm, small, hint));
   mark(5);
@@ -536,7 +549,7 @@ int slot_launch(sdsj_engine* e, Slot& sl, int n, size_t bytes, const sdsj_op& op
       if (sl.h_pre[i] != SDSJ_OK) continue;
       int st = SDSJ_OK;
       uint64_t r = 0;
-      const int64_t ni = host_plan_need(sl.h_stage + sl.h_offsets[i], sl.h_lengths[i], op, &st, &r, small);
+      const int64_t ni = host_plan_need(sl.h_stage + sl.h_offsets[i], sl.h_lengths[i], op, &st, &r, small, e->formats);
       if (st == SDSJ_OK) needs[i] = align_up(ni, 256);
       rm |= r;
     }
@@ -715,6 +728,22 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
   return st;
 }
 
+int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need) {
+  if (!img || !need || !valid_op(op) || !(formats & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG))) return SDSJ_EINVAL;
+  int st = SDSJ_OK;
+  const int64_t b = host_plan_need(img, (int64_t)n, *op, &st, nullptr, false, formats);
+  *need = st == SDSJ_OK ? align_up(b, 256) : 0;
+  return st;
+}
+
+int sdsj_engine_set_formats(sdsj_engine* e, int mask) {
+  if (!e) return SDSJ_EINVAL;
+  if (!(mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) || (mask & ~(SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)))
+    return fail(e, SDSJ_EINVAL, "invalid format mask");
+  e->formats = mask;
+  return SDSJ_OK;
+}
+
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out) {
   if (!out) return SDSJ_EINVAL;
   *out = nullptr;
@@ -856,7 +885,7 @@ int sdsj_decode_resize_batch(sdsj_engine* e, int n, const uint8_t* const* jpg, c
       int st = SDSJ_OK;
       if (len[c0 + i] > (size_t)INT32_MAX) return fail(e, SDSJ_EINVAL, "sample larger than 2 GiB");
       uint64_t r = 0;
-      int64_t ni = host_plan_need(jpg[c0 + i], (int64_t)len[c0 + i], *op, &st, &r, small);
+      int64_t ni = host_plan_need(jpg[c0 + i], (int64_t)len[c0 + i], *op, &st, &r, small, e->formats);
       if (st == SDSJ_OK) need += align_up(ni, 256);
       rm |= r;
       bytes += align_up((int64_t)len[c0 + i], 16);
@@ -988,7 +1017,8 @@ int sdsj_engine_stage_times(const sdsj_engine* e, float* ms, int cap, int* n_sta
   for (size_t c = 0; c < e->ev_used; c++) {
     for (int k = 0; k < cap && k < kStages; k++) {
       float v = 0.f;
-      if (hipEventElapsedTime(&v, e->ev_sets[c][k], e->ev_sets[c][k + 1]) != hipSuccess) return SDSJ_EHIP;
+      const int ev = stage_event(k);
+      if (hipEventElapsedTime(&v, e->ev_sets[c][ev], e->ev_sets[c][ev + 1]) != hipSuccess) return SDSJ_EHIP;
       ms[k] += v;
     }
   }
@@ -1027,7 +1057,8 @@ int sdsj_engine_counters(sdsj_engine* e, uint64_t* out, int cap, int reset) {
 
 const char* sdsj_counter_name(int k) {
   static const char* names[SDSJ_NUM_COUNTERS] = {"images",    "ok",        "unsupported", "corrupt", "capacity",
-                                                 "other",     "bytes_in",  "bytes_out",   "frames",  "progressive"};
+                                                 "other",     "bytes_in",  "bytes_out",   "frames",  "progressive",
+                                                 "png"};
   return k >= 0 && k < SDSJ_NUM_COUNTERS ? names[k] : "";
 }
 

@@ -125,7 +125,7 @@ __device__ __forceinline__ bool variant_owns(int ns) {
 __global__ void __launch_bounds__(kEntThreads) k_enttab(ImgDesc* __restrict__ descs,
                                                        const ImgTables* __restrict__ tables, EntTables* __restrict__ out) {
   ImgDesc* d = &descs[blockIdx.x];
-  if (d->status != SDSJ_OK || d->progressive) return;
+  if (d->status != SDSJ_OK || d->progressive || d->png) return;
   const ImgTables* tb = &tables[blockIdx.x];
   __shared__ LutTables T;  // (the multi-symbol table goes straight to HBM: nothing here reads it back)
   __shared__ int32_t lim[kMaxSlots][12];

@@ -20,8 +20,15 @@ inline unsigned route_grid(uint64_t hint, int r, int64_t full) {
   return (unsigned)(route_on(hint, r) || full < kColdGrid ? full : kColdGrid);
 }
 // blob_bytes: the blob's size -- a sample whose [offset, offset + length) leaves it is reported EINVAL
+// formats: SDSJ_FORMAT_* mask of the engine (samples of a format outside it report SDSJ_UNSUPPORTED)
 hipError_t launch_parse(int n, const uint8_t* blob, int64_t blob_bytes, const int64_t* offsets, const int32_t* lengths,
-                        const sdsj_op& op, int warm_bits, bool small, ImgDesc* descs, ImgTables* tables, hipStream_t s);
+                        const sdsj_op& op, int warm_bits, bool small, ImgDesc* descs, ImgTables* tables, hipStream_t s,
+                        int formats = SDSJ_FORMAT_JPEG);
+// PNG samples (route kRtPng): k_png_inflate then k_png_unfilter (sdsj_png.hip); `between` (optional) is
+// recorded between the two
+hipError_t launch_png(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                      uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
+                      uint64_t hint = kAllRoutes, hipEvent_t between = nullptr);
 // base: scratch bytes a previous lane of the batch already took (device), or null
 hipError_t launch_plan(int n, ImgDesc* descs, int64_t capacity, const int64_t* base, int64_t* total, int32_t* routes,
                        int cap, hipStream_t s);
@@ -69,7 +76,7 @@ hipError_t launch_finish(int n, ImgDesc* descs, const sdsj_op& op, void* out, in
 // parse fails, so the device's own verdict is never starved of a kernel)
 // small: the latency-mode plan of a chunk of at most kSmallBatch images (k_parse's `small`)
 int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* status, uint64_t* routes = nullptr,
-                       bool small = false);
+                       bool small = false, int formats = SDSJ_FORMAT_JPEG);
 // host-side planning of one raw RGB frame (width x height) for the unfused passes; returns scratch bytes
 int64_t host_plan_frame(ImgDesc* d, int width, int height, const sdsj_op& op);
 }  // namespace sdsj

@@ -20,6 +20,7 @@
 #include "sdsj_common.h"
 #include "sdsj_kernels.h"
 #include "sdsj_idct.h"
+#include "sdsj_png.h"
 
 #pragma clang fp contract(off)
 
@@ -74,7 +75,10 @@ __device__ __host__ inline int huff_slots(const ImgDesc& d) {
   return ns;
 }
 
-__device__ __host__ inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = false, bool small = false) {
+// png = true: a PNG sample: like a frame it resamples through the unfused passes, from RGB rows that
+// k_png_unfilter packs at off_rgb; its inflated scanlines take off_png.
+__device__ __host__ inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = false, bool small = false,
+                                              bool png = false) {
   // Geometry: functional.py:78-80 shortcut, :118-147 crop, Pillow ImagingResampleInner.
   const int W = d->width, H = d->height;
   if (W == op.out_w && H == op.out_h) {
@@ -145,7 +149,7 @@ __device__ __host__ inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, boo
       tw = (tw + 1) / 2;
     }
   }
-  if (frames) d->fused = 0;
+  if (frames || png) d->fused = 0;
   // specialised fused kernels (sdsj_resample420.hip): 4:2:0 (h2v2 fancy chroma), 4:2:2 (h2v1 fancy
   // chroma), 4:4:4 and grayscale, horizontal and vertical passes, odd tap counts 3..11; everything
   // else takes the generic k_resample
@@ -166,7 +170,7 @@ __device__ __host__ inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, boo
       d->rs_lay = lay;
     }
   }
-  d->lat = small && !frames;
+  d->lat = small && !frames && !png;
   // multi-hypothesis speculative pass for latency-mode baseline images without restart intervals;
   // only the 11-bit entropy routes launch it (k_entspec_mh), so images of more than 4 table slots
   // (kRtEnt10) keep the ordinary speculative pass
@@ -177,7 +181,7 @@ __device__ __host__ inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, boo
     const int64_t per_group = (int64_t)kDecodeThreads * (d->lat ? kLatSubBits : kGroupBits);
     int64_t g = (bits + per_group - 1) / per_group;
     g = g < 1 ? 1 : (g > kMaxEntGroups ? kMaxEntGroups : g);
-    d->ent_groups = frames ? 1 : (int32_t)g;
+    d->ent_groups = frames || png ? 1 : (int32_t)g;
     const int64_t lanes = (int64_t)kDecodeThreads * d->ent_groups;
     d->sub_bits = (int32_t)align_up((bits + lanes - 1) / lanes, 32);
   }
@@ -217,6 +221,7 @@ __device__ __host__ inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, boo
   d->off_tmp = take(!d->fused && d->need_h ? (int64_t)(d->yl - d->yf) * op.out_w * 3 : 0);
   d->off_kh = take(d->need_h ? ((int64_t)2 * op.out_w + (int64_t)op.out_w * d->ksh) * 4 : 0);
   d->off_kv = take(d->need_v ? ((int64_t)2 * op.out_h + (int64_t)op.out_h * d->ksv) * 4 : 0);
+  d->off_png = take(png ? d->png_raw + 64 : 0);
   d->need = o;
   return o;
 }
@@ -254,7 +259,7 @@ struct DevSink {
 __global__ void __launch_bounds__(64) k_parse(int n, const uint8_t* __restrict__ blob, int64_t blob_bytes,
                                               const int64_t* __restrict__ offsets, const int32_t* __restrict__ lengths,
                                               sdsj_op op, int warm_bits, int small, ImgDesc* __restrict__ descs,
-                                              ImgTables* __restrict__ tables) {
+                                              ImgTables* __restrict__ tables, int formats) {
   const int img = blockIdx.x;
   if (img >= n) return;
   const int lane = threadIdx.x;
@@ -280,9 +285,20 @@ __global__ void __launch_bounds__(64) k_parse(int n, const uint8_t* __restrict__
   DevReader rd{hdr, nstage, g};
   if (lane == 0) {
     DevSink sink{jobs, &njobs, rd};
-    int status = parse_headers(rd, len, &sd, &st, sink);
-    if (status == SDSJ_OK) status = setup_geometry(&sd, &st);
-    if (status == SDSJ_OK) plan_image(&sd, op, false, small != 0);
+    int status;
+    sd.png = 0;
+    if ((formats & SDSJ_FORMAT_PNG) && png_signature(rd, len)) {
+      PngHdr ph;
+      status = png_parse(rd, len, &ph);
+      png_fill_desc(&sd, ph);
+      if (status == SDSJ_OK) plan_image(&sd, op, false, false, true);
+    } else if (!(formats & SDSJ_FORMAT_JPEG)) {
+      status = SDSJ_UNSUPPORTED;
+    } else {
+      status = parse_headers(rd, len, &sd, &st, sink);
+      if (status == SDSJ_OK) status = setup_geometry(&sd, &st);
+      if (status == SDSJ_OK) plan_image(&sd, op, false, small != 0);
+    }
     if (warm_bits >= 0) sd.warm_bits = warm_bits;  // override (experiments)
     else if (n < kWarmSmallLane && !sd.lat) sd.warm_bits = warm_for(sd.sub_bits, kWarmBitsSmall);  // small lane
     sd.status = status;
@@ -330,6 +346,12 @@ __global__ void __launch_bounds__(64) k_parse(int n, const uint8_t* __restrict__
 // progressive images), entropy variant by the Huffman tables in use (slots as load_tables counts
 // them), resample variant as plan_image chose it (-1 for an empty crop).
 SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
+  if (d.png) {
+    *ru = -1;
+    *re = kRtPng;
+    *rr = d.geo == kGeoZeros ? -1 : kRtUnfused;
+    return;
+  }
   const int ns = huff_slots(d);
   *ru = d.progressive ? -1 : (d.ntiles > kUsSerialTiles || d.lat ? kRtUsBig : kRtUsSmall);
   *re = d.progressive ? kRtProg : ns > 4 ? kRtEnt10 : (d.ent_groups > 1 ? kRtEnt11M : kRtEnt11);
@@ -397,6 +419,7 @@ __global__ void __launch_bounds__(kPlanThreads) k_plan_apply(int n, ImgDesc* __r
       d.off_tmp += start;
       d.off_kh += start;
       d.off_kv += start;
+      d.off_png += start;
       // routes (image_routes): unstuffing -- one workgroup per small image, tile-parallel passes for
       // the rest --, entropy variant, resample variant
       image_routes(d, &ru, &re, &rr);
@@ -447,6 +470,7 @@ __global__ void __launch_bounds__(256) k_finish(int n, const ImgDesc* __restrict
       if (lengths && lengths[img] > 0) atomicAdd(&acc[SDSJ_CTR_BYTES_IN], (unsigned long long)lengths[img]);
       atomicAdd(&acc[SDSJ_CTR_BYTES_OUT], (unsigned long long)(total * (op.out_dtype == SDSJ_DTYPE_F32 ? 4 : 1)));
       if (lengths && st == SDSJ_OK && d->progressive) atomicAdd(&acc[SDSJ_CTR_PROGRESSIVE], 1ull);
+      if (lengths && st == SDSJ_OK && d->png) atomicAdd(&acc[SDSJ_CTR_PNG], 1ull);
     }
   }
   __syncthreads();
@@ -1071,7 +1095,7 @@ __global__ void __launch_bounds__(64) k_scanmap(int n, const uint8_t* __restrict
   const int img = blockIdx.x * 64 + threadIdx.x;
   if (img >= n) return;
   ImgDesc* d = &descs[img];
-  if (d->status != SDSJ_OK || d->progressive) return;  // progressive: k_prog reads the raw stream
+  if (d->status != SDSJ_OK || d->progressive || d->png) return;  // progressive: k_prog reads the raw stream
   const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
   finish_scan(d, sv, blob + offsets[img], d->entropy_len, d->useg_found - 1, d->scan_end_code, d->scan_end_raw, d->ulen, 0);
 }
@@ -1108,7 +1132,7 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
   const int img = blockIdx.y;
   if (img >= n) return;
   const ImgDesc* d = &descs[img];
-  if (d->status != SDSJ_OK || d->geo == kGeoZeros) return;
+  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->png) return;
   int nwg = gridDim.x;  // this image's workgroups
   if (SDSJ_IDCT_GPW > 0 && gridDim.x == kIdctGridMax) {
     const int64_t want = ((int64_t)d->total_blocks / 8 + SDSJ_IDCT_GPW - 1) / SDSJ_IDCT_GPW;
@@ -1313,7 +1337,7 @@ __global__ void __launch_bounds__(256) k_color(int n, const ImgDesc* __restrict_
  for (int li = blockIdx.y; li < routes[kRtUnfused]; li += gridDim.y) {
   const int img = rl[li];
   const ImgDesc* d = &descs[img];
-  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->fused) continue;
+  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->fused || d->png) continue;  // (PNG rows: k_png_unfilter)
   const int w = d->src_w, h = d->src_y1 - d->src_y0;
   const int64_t total = (int64_t)w * h;
   const uint8_t* planes = scratch + d->off_planes;
@@ -1580,9 +1604,10 @@ __global__ void __launch_bounds__(256) k_vpass(int n, const ImgDesc* __restrict_
 // Host-side launchers (called by the engine; all asynchronous on `stream`).
 // ------------------------------------------------------------------------------------------
 hipError_t launch_parse(int n, const uint8_t* blob, int64_t blob_bytes, const int64_t* offsets, const int32_t* lengths,
-                        const sdsj_op& op, int warm_bits, bool small, ImgDesc* descs, ImgTables* tables, hipStream_t s) {
+                        const sdsj_op& op, int warm_bits, bool small, ImgDesc* descs, ImgTables* tables, hipStream_t s,
+                        int formats) {
   hipLaunchKernelGGL(k_parse, dim3(n), dim3(64), 0, s, n, blob, blob_bytes, offsets, lengths, op, warm_bits, (int)small,
-                     descs, tables);
+                     descs, tables, formats);
   return hipGetLastError();
 }
 hipError_t launch_plan(int n, ImgDesc* descs, int64_t capacity, const int64_t* base, int64_t* total, int32_t* routes,
@@ -1677,14 +1702,26 @@ int64_t host_plan_frame(ImgDesc* d, int width, int height, const sdsj_op& op) {
   return plan_image(d, op, true);
 }
 
-int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* status, uint64_t* routes, bool small) {
+int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* status, uint64_t* routes, bool small,
+                       int formats) {
   ImgDesc d;
   static thread_local ImgTables t;
   HostReader rd{jpg};
-  int st = parse_headers(rd, n, &d, &t, CopySink<HostReader>{rd});
-  if (st == SDSJ_OK) st = setup_geometry(&d, &t);
+  int st;
   int64_t need = 0;
-  if (st == SDSJ_OK) need = plan_image(&d, op, false, small);
+  d.png = 0;
+  if ((formats & SDSJ_FORMAT_PNG) && png_signature(rd, n)) {  // (as k_parse)
+    PngHdr ph;
+    st = png_parse(rd, n, &ph);
+    png_fill_desc(&d, ph);
+    if (st == SDSJ_OK) need = plan_image(&d, op, false, false, true);
+  } else if (!(formats & SDSJ_FORMAT_JPEG)) {
+    st = SDSJ_UNSUPPORTED;
+  } else {
+    st = parse_headers(rd, n, &d, &t, CopySink<HostReader>{rd});
+    if (st == SDSJ_OK) st = setup_geometry(&d, &t);
+    if (st == SDSJ_OK) need = plan_image(&d, op, false, small);
+  }
   *status = st;
   if (routes) {
     *routes = kAllRoutes;

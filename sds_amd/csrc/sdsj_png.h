@@ -1,0 +1,558 @@
+// sdsj_png.h -- the PNG subset the MI355X path decodes, as functions shared by the host (sdsj_png_probe,
+// host planning, the serial decoder of tests/asan/png_driver.cpp) and the device (k_parse,
+// k_png_inflate, k_png_unfilter in sdsj_png.hip).  Every decision about correctness or bounds is taken
+// here; the kernels add only the lane-parallel movement of bytes.
+//
+// Reference behaviour: PIL.Image.open(...).convert("RGB") (PngImagePlugin.py + ZipDecode.c + zlib).
+// Subset: non-interlaced, bit depth 8, colour types 0, 2, 3, 4, 6.  The rule is exactness: a sample is
+// reported SDSJ_OK only where PIL decodes the same bytes to the same pixels without raising; everything
+// this code is not sure about is SDSJ_UNSUPPORTED (a valid file outside the subset) or SDSJ_CORRUPT
+// (anything malformed), and the transforms rerun both on PIL, which then decides.
+#pragma once
+#include <stdint.h>
+
+#include "sdsj_common.h"
+
+// Functions that take the bit reader are inlined into the kernel: its state then lives in registers
+// (a call would keep it in memory behind a reference).
+#if defined(__HIPCC__)
+#define SDSJ_HDI __host__ __device__ __attribute__((always_inline)) inline
+#else
+#define SDSJ_HDI inline
+#endif
+
+namespace sdsj {
+
+struct PngHdr {
+  int32_t width, height, bit_depth, ctype, interlace;
+  int32_t bpp;       // bytes per pixel of the scanlines (bit depth 8)
+  int32_t plte_n;    // PLTE entries (0: none)
+  int32_t zero;
+  int64_t plte_pos;  // first PLTE data byte
+  int64_t idat_pos;  // length field of the first IDAT chunk
+};
+
+constexpr int64_t kPngMaxPixels = 89478485;      // PIL Image.MAX_IMAGE_PIXELS: above it Image.open warns or raises
+constexpr int64_t kPngMaxHeader = 1 << 20;       // bytes before the first IDAT this path walks
+constexpr int64_t kPngMaxRaw = (int64_t)1 << 30;  // inflated scanline bytes of one image
+
+SDSJ_HD inline uint32_t png_crc_byte(uint32_t c, int b) {  // CRC-32 (reflected 0xEDB88320), one byte, no table
+  c ^= (uint32_t)b;
+  for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+  return c;
+}
+
+template <class Reader>
+SDSJ_HDI uint32_t png_be32(const Reader& rd, int64_t i) {
+  return ((uint32_t)rd(i) << 24) | ((uint32_t)rd(i + 1) << 16) | ((uint32_t)rd(i + 2) << 8) | (uint32_t)rd(i + 3);
+}
+
+SDSJ_HD inline uint32_t png_tag(char a, char b, char c, char d) {
+  return ((uint32_t)(uint8_t)a << 24) | ((uint32_t)(uint8_t)b << 16) | ((uint32_t)(uint8_t)c << 8) | (uint32_t)(uint8_t)d;
+}
+
+template <class Reader>
+SDSJ_HD inline bool png_signature(const Reader& rd, int64_t n) {
+  return n >= 8 && rd(0) == 0x89 && rd(1) == 'P' && rd(2) == 'N' && rd(3) == 'G' && rd(4) == 0x0D && rd(5) == 0x0A &&
+         rd(6) == 0x1A && rd(7) == 0x0A;
+}
+
+// Signature, IHDR, the chunks before the first IDAT.  Image.open reads exactly these chunks and
+// verifies the CRC of each (PngImagePlugin.py ChunkStream.crc), so a mismatch in any of them is an
+// error there; a chunk whose handler could raise or that this path has not been checked against
+// (iCCP, zTXt, iTXt, acTL, ... and unknown ones) hands the sample over instead of guessing.
+// h's IHDR fields are filled as soon as IHDR has been read, whatever the status.
+template <class Reader>
+SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h) {
+  h->width = h->height = h->bit_depth = h->ctype = h->interlace = h->bpp = h->plte_n = h->zero = 0;
+  h->plte_pos = h->idat_pos = 0;
+  if (!png_signature(rd, n)) return SDSJ_UNSUPPORTED;
+  int64_t p = 8;
+  bool first = true;
+  for (;;) {
+    if (p + 12 > n) return SDSJ_CORRUPT;  // no room for length, type and CRC
+    if (p > kPngMaxHeader) return SDSJ_UNSUPPORTED;
+    const uint32_t len = png_be32(rd, p), tag = png_tag((char)rd(p + 4), (char)rd(p + 5), (char)rd(p + 6), (char)rd(p + 7));
+    if (first != (tag == png_tag('I', 'H', 'D', 'R'))) return first ? SDSJ_CORRUPT : SDSJ_UNSUPPORTED;
+    if (tag == png_tag('I', 'D', 'A', 'T')) {
+      h->idat_pos = p;
+      break;
+    }
+    if (len > (uint32_t)kPngMaxHeader || p + 12 + (int64_t)len > n) return SDSJ_CORRUPT;
+    if (first) {
+      if (len != 13) return SDSJ_CORRUPT;
+      h->width = (int32_t)png_be32(rd, p + 8);
+      h->height = (int32_t)png_be32(rd, p + 12);
+      h->bit_depth = rd(p + 16);
+      h->ctype = rd(p + 17);
+      h->interlace = rd(p + 20);
+    }
+    uint32_t crc = 0xFFFFFFFFu;
+    for (int64_t i = p + 4; i < p + 8 + (int64_t)len; i++) crc = png_crc_byte(crc, rd(i));
+    if ((crc ^ 0xFFFFFFFFu) != png_be32(rd, p + 8 + len)) return SDSJ_CORRUPT;
+    if (first) {
+      first = false;
+      if (h->width <= 0 || h->height <= 0 || rd(p + 18) != 0 || rd(p + 19) != 0 || h->interlace > 1) return SDSJ_CORRUPT;
+      const int ct = h->ctype, bd = h->bit_depth;
+      const bool pow2 = bd == 1 || bd == 2 || bd == 4 || bd == 8 || bd == 16;
+      const bool legal = pow2 && (ct == 0 || (ct == 3 && bd <= 8) || ((ct == 2 || ct == 4 || ct == 6) && bd >= 8));
+      if (!legal) return SDSJ_CORRUPT;
+      h->bpp = ct == 0 || ct == 3 ? 1 : ct == 4 ? 2 : ct == 2 ? 3 : 4;
+    } else if (tag == png_tag('P', 'L', 'T', 'E')) {
+      if (h->plte_n || len == 0 || len > 768 || len % 3) return SDSJ_UNSUPPORTED;
+      h->plte_n = (int32_t)(len / 3);
+      h->plte_pos = p + 8;
+    } else if (tag == png_tag('t', 'R', 'N', 'S')) {  // ignored by convert("RGB"); its handler indexes by colour type
+      if (len > 256 || (h->ctype == 0 && len != 2) || (h->ctype == 2 && len != 6)) return SDSJ_UNSUPPORTED;
+    } else if (tag == png_tag('g', 'A', 'M', 'A')) {
+      if (len != 4) return SDSJ_UNSUPPORTED;
+    } else if (tag == png_tag('c', 'H', 'R', 'M')) {
+      if (len != 32) return SDSJ_UNSUPPORTED;
+    } else if (tag == png_tag('s', 'R', 'G', 'B')) {
+      if (len != 1) return SDSJ_UNSUPPORTED;
+    } else if (tag == png_tag('p', 'H', 'Y', 's')) {
+      if (len != 9) return SDSJ_UNSUPPORTED;
+    } else if (tag == png_tag('t', 'E', 'X', 't')) {
+      if (len > 65536) return SDSJ_UNSUPPORTED;
+    } else {
+      return SDSJ_UNSUPPORTED;  // acTL (APNG), iCCP, zTXt, iTXt, eXIf, unknown chunks: PIL decides
+    }
+    p += 12 + (int64_t)len;
+  }
+  if (first) return SDSJ_CORRUPT;
+  if (h->interlace || h->bit_depth != 8) return SDSJ_UNSUPPORTED;
+  if ((int64_t)h->width * h->height > kPngMaxPixels || h->width > 65535 || h->height > 65535) return SDSJ_UNSUPPORTED;
+  if ((int64_t)h->height * (1 + (int64_t)h->width * h->bpp) > kPngMaxRaw) return SDSJ_UNSUPPORTED;
+  return SDSJ_OK;
+}
+
+SDSJ_HD inline int64_t png_raw_bytes(int w, int h, int bpp) { return (int64_t)h * (1 + (int64_t)w * bpp); }
+
+// ------------------------------------------------------------------------------------------
+// Bit reader over the IDAT chain (LSB first, RFC 1951).  At the end of a chunk's payload it skips the
+// CRC (PIL does not check IDAT CRCs) and reads the next length and type; a type other than IDAT, a
+// chunk that leaves the input, or the end of the input end the data.  No byte outside [0, n) is read.
+// ------------------------------------------------------------------------------------------
+template <class Reader>
+struct PngBits {
+  Reader rd;  // (by value: a reader with state, such as the device's LDS window, keeps it in registers)
+  int64_t n, pos, chunk_end;
+  uint64_t buf;
+  int32_t cnt;
+  int32_t ended;  // no more IDAT data
+};
+
+template <class Reader>
+SDSJ_HDI bool png_hop(PngBits<Reader>& b) {  // positions on the next IDAT payload byte; false: none
+  while (b.pos == b.chunk_end) {
+    if (b.ended) return false;
+    const int64_t q = b.chunk_end + 4;  // past the CRC
+    if (q + 8 > b.n) {
+      b.ended = 1;
+      return false;
+    }
+    const uint32_t len = png_be32(b.rd, q), tag = png_be32(b.rd, q + 4);
+    if (tag != png_tag('I', 'D', 'A', 'T') || len > 0x7FFFFFFFu || q + 8 + (int64_t)len > b.n) {
+      b.ended = 1;
+      return false;
+    }
+    b.pos = q + 8;
+    b.chunk_end = b.pos + (int64_t)len;
+  }
+  return true;
+}
+
+template <class Reader>
+SDSJ_HDI void png_bits_init(PngBits<Reader>& b, const Reader& rd, int64_t n, int64_t idat_pos) {
+  b.rd = rd;
+  b.n = n;
+  b.buf = 0;
+  b.cnt = 0;
+  b.ended = 0;
+  // idat_pos is the first IDAT's length field: enter it as if a previous chunk's CRC ended 4 bytes before
+  b.pos = b.chunk_end = idat_pos - 4;
+}
+
+template <class Reader>
+SDSJ_HDI void png_fill(PngBits<Reader>& b) {  // as many whole bytes as fit below 57 bits
+  if (b.chunk_end - b.pos >= 8 && b.cnt <= 48) {  // inside a chunk: eight independent reads, the bytes that fit are kept
+    uint64_t v = 0;
+    for (int j = 0; j < 8; j++) v |= (uint64_t)(uint32_t)b.rd(b.pos + j) << (8 * j);
+    const int k = (56 - b.cnt) >> 3;  // 1..7 bytes
+    v &= (1ull << (8 * k)) - 1;
+    b.buf |= v << b.cnt;
+    b.pos += k;
+    b.cnt += 8 * k;
+    return;
+  }
+  while (b.cnt <= 48) {
+    if (b.pos == b.chunk_end && !png_hop(b)) return;
+    b.buf |= (uint64_t)(uint32_t)b.rd(b.pos++) << b.cnt;
+    b.cnt += 8;
+  }
+}
+
+template <class Reader>
+SDSJ_HDI bool png_take(PngBits<Reader>& b, int k, uint32_t* v) {  // k <= 32 bits, false: data exhausted
+  if (b.cnt < k) png_fill(b);
+  if (b.cnt < k) return false;
+  *v = (uint32_t)(b.buf & ((1ull << k) - 1));
+  b.buf >>= k;
+  b.cnt -= k;
+  return true;
+}
+
+// What follows the image data.  PIL's load_end walks the chunks after the last IDAT it consumed and
+// calls their handlers, which can raise; this path accepts only what it is sure of: further IDAT
+// chunks (skipped there too), then IEND or the end of the input.
+template <class Reader>
+SDSJ_HDI bool png_tail_ok(PngBits<Reader>& b) {
+  for (;;) {
+    b.pos = b.chunk_end;
+    if (png_hop(b)) continue;
+    const int64_t q = b.chunk_end + 4;
+    if (q + 8 > b.n) return true;  // the input ends: PIL stops on the short read
+    const uint32_t len = png_be32(b.rd, q), tag = png_be32(b.rd, q + 4);
+    return tag == png_tag('I', 'E', 'N', 'D') && len == 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Deflate tables: canonical counts and sorted symbols (the search for long codes) plus a first-level
+// lookup of kInfLut bits: entry = symbol << 4 | code length, 0 = a longer or unused code.
+// ------------------------------------------------------------------------------------------
+constexpr int kInfLutBits = 9;
+constexpr int kInfLut = 1 << kInfLutBits;
+
+struct InfCode {
+  uint16_t cnt[16];
+  uint16_t lut[kInfLut];
+};
+
+struct InfTables {
+  InfCode ll, d;
+  uint16_t ll_sym[288];
+  uint16_t d_sym[32];
+  uint8_t lens[320];  // 288 + 32
+};
+
+SDSJ_HD inline uint32_t inf_rev(uint32_t code, int len) {
+  uint32_t r = 0;
+  for (int k = 0; k < len; k++) r |= ((code >> k) & 1u) << (len - 1 - k);
+  return r;
+}
+
+// zlib inftrees.c inflate_table's checks: an over-subscribed set is an error; an incomplete set is an
+// error unless its longest code has one bit (`strict`: the dynamic blocks' literal/length and distance
+// sets); a set without any code is accepted, and every code of it is then invalid.
+SDSJ_HD inline bool inf_build(const uint8_t* lens, int n, InfCode* c, uint16_t* sym, bool strict) {
+  for (int l = 0; l < 16; l++) c->cnt[l] = 0;
+  for (int i = 0; i < n; i++) c->cnt[lens[i] & 15]++;
+  for (int i = 0; i < kInfLut; i++) c->lut[i] = 0;
+  int left = 1, maxl = 0;
+  for (int l = 1; l < 16; l++) {
+    left <<= 1;
+    left -= c->cnt[l];
+    if (left < 0) return false;
+    if (c->cnt[l]) maxl = l;
+  }
+  if (maxl == 0) {
+    c->cnt[0] = (uint16_t)n;
+    return true;
+  }
+  if (left > 0 && strict && maxl != 1) return false;
+  uint16_t offs[16], next[16];
+  offs[1] = 0;
+  next[0] = 0;
+  next[1] = 0;
+  uint32_t code = 0;
+  for (int l = 1; l < 15; l++) offs[l + 1] = (uint16_t)(offs[l] + c->cnt[l]);
+  for (int l = 1; l < 16; l++) {
+    code = (code + (l > 1 ? c->cnt[l - 1] : 0)) << (l > 1 ? 1 : 0);
+    next[l] = (uint16_t)code;
+  }
+  for (int i = 0; i < n; i++) {
+    const int l = lens[i] & 15;
+    if (!l) continue;
+    sym[offs[l]++] = (uint16_t)i;
+    const uint32_t cd = next[l]++;
+    if (l <= kInfLutBits) {
+      const uint32_t r = inf_rev(cd, l);
+      for (uint32_t k = r; k < (uint32_t)kInfLut; k += 1u << l) c->lut[k] = (uint16_t)((i << 4) | l);
+    }
+  }
+  return true;
+}
+
+// One symbol: -1 = invalid code or data exhausted.
+template <class Reader>
+SDSJ_HDI int inf_decode(PngBits<Reader>& b, const InfCode* c, const uint16_t* sym) {
+  if (b.cnt < 15) png_fill(b);
+  const uint32_t e = c->lut[b.buf & (kInfLut - 1)];
+  if (e) {
+    const int l = (int)(e & 15);
+    if (l > b.cnt) return -1;
+    b.buf >>= l;
+    b.cnt -= l;
+    return (int)(e >> 4);
+  }
+  int code = 0, first = 0, index = 0;
+  for (int l = 1; l <= 15; l++) {
+    if (l > b.cnt) return -1;
+    code |= (int)((b.buf >> (l - 1)) & 1);
+    const int count = c->cnt[l];
+    if (code - count < first) {
+      b.buf >>= l;
+      b.cnt -= l;
+      return sym[index + (code - first)];
+    }
+    index += count;
+    first += count;
+    first <<= 1;
+    code <<= 1;
+  }
+  return -1;
+}
+
+SDSJ_HD inline void inf_fixed_lens(uint8_t* lens) {
+  for (int i = 0; i < 144; i++) lens[i] = 8;
+  for (int i = 144; i < 256; i++) lens[i] = 9;
+  for (int i = 256; i < 280; i++) lens[i] = 7;
+  for (int i = 280; i < 288; i++) lens[i] = 8;
+  for (int i = 0; i < 32; i++) lens[288 + i] = 5;
+}
+
+// Block header.  type 0: *stored = LEN (the reader is byte-aligned on its first byte); 1 / 2: T holds
+// the block's tables.  False: an error (type 3, LEN/NLEN mismatch, bad code lengths, data exhausted).
+template <class Reader>
+SDSJ_HDI bool inf_block_header(PngBits<Reader>& b, InfTables* T, int* final, int* type, int* stored) {
+  uint32_t v;
+  if (!png_take(b, 3, &v)) return false;
+  *final = (int)(v & 1);
+  *type = (int)(v >> 1);
+  if (*type == 3) return false;
+  if (*type == 0) {
+    const int drop = b.cnt & 7;  // whole bytes are buffered: the bits up to the byte boundary
+    b.buf >>= drop;
+    b.cnt -= drop;
+    if (!png_take(b, 32, &v)) return false;
+    if ((v & 0xFFFFu) != ((v >> 16) ^ 0xFFFFu)) return false;
+    *stored = (int)(v & 0xFFFFu);
+    return true;
+  }
+  if (*type == 1) {
+    inf_fixed_lens(T->lens);
+    return inf_build(T->lens, 288, &T->ll, T->ll_sym, false) && inf_build(T->lens + 288, 32, &T->d, T->d_sym, false);
+  }
+  if (!png_take(b, 14, &v)) return false;
+  const int nlen = (int)(v & 31) + 257, ndist = (int)((v >> 5) & 31) + 1, ncode = (int)(v >> 10) + 4;
+  if (nlen > 286 || ndist > 30) return false;
+  const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+  uint8_t cl[19];
+  for (int i = 0; i < 19; i++) cl[i] = 0;
+  for (int i = 0; i < ncode; i++) {
+    if (!png_take(b, 3, &v)) return false;
+    cl[order[i]] = (uint8_t)v;
+  }
+  // the code-length code is decoded with the distance table's storage (rebuilt below)
+  if (!inf_build(cl, 19, &T->d, T->d_sym, false)) return false;
+  {  // inflate_table(CODES): an incomplete code-length code is an error
+    int left = 1;
+    for (int l = 1; l < 16; l++) left = (left << 1) - T->d.cnt[l];
+    if (left > 0) return false;
+  }
+  int i = 0;
+  while (i < nlen + ndist) {
+    const int s = inf_decode(b, &T->d, T->d_sym);
+    if (s < 0) return false;
+    if (s < 16) {
+      T->lens[i++] = (uint8_t)s;
+      continue;
+    }
+    int rep, val = 0;
+    if (s == 16) {
+      if (i == 0 || !png_take(b, 2, &v)) return false;
+      val = T->lens[i - 1];
+      rep = 3 + (int)v;
+    } else if (s == 17) {
+      if (!png_take(b, 3, &v)) return false;
+      rep = 3 + (int)v;
+    } else {
+      if (!png_take(b, 7, &v)) return false;
+      rep = 11 + (int)v;
+    }
+    if (i + rep > nlen + ndist) return false;
+    while (rep--) T->lens[i++] = (uint8_t)val;
+  }
+  if (T->lens[256] == 0) return false;  // no end-of-block code
+  // the distance lengths follow the literal/length ones: move them before ll's build reuses nothing of
+  // them (separate arrays), then build both sets
+  uint8_t dl[32];
+  for (int k = 0; k < ndist; k++) dl[k] = T->lens[nlen + k];
+  for (int k = 0; k < ndist; k++) T->lens[288 + k] = dl[k];
+  return inf_build(T->lens, nlen, &T->ll, T->ll_sym, true) && inf_build(T->lens + 288, ndist, &T->d, T->d_sym, true);
+}
+
+// Length / distance of a match from its symbol (base + extra bits).  False: invalid symbol or data exhausted.
+template <class Reader>
+SDSJ_HDI bool inf_length(PngBits<Reader>& b, int sym, int* len) {
+  const uint16_t base[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+  const uint8_t ext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+  const int k = sym - 257;
+  if (k < 0 || k >= 29) return false;
+  uint32_t v = 0;
+  if (ext[k] && !png_take(b, ext[k], &v)) return false;
+  *len = base[k] + (int)v;
+  return true;
+}
+
+template <class Reader>
+SDSJ_HDI bool inf_distance(PngBits<Reader>& b, const InfTables* T, int* dist) {
+  const uint16_t base[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+  const uint8_t ext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+  const int s = inf_decode(b, &T->d, T->d_sym);
+  if (s < 0 || s >= 30) return false;
+  uint32_t v = 0;
+  if (ext[s] && !png_take(b, ext[s], &v)) return false;
+  *dist = base[s] + (int)v;
+  return true;
+}
+
+// A match is valid when its source lies inside the bytes produced so far and inside the window the
+// zlib header declares, and its end inside the expected output.
+SDSJ_HD inline bool inf_match_ok(int64_t produced, int64_t expect, int dist, int len, int window) {
+  return dist >= 1 && (int64_t)dist <= produced && dist <= window && produced + len <= expect;
+}
+
+// zlib header (RFC 1950): deflate, window <= 32 KiB, check bits, no preset dictionary.
+template <class Reader>
+SDSJ_HDI bool zlib_header(PngBits<Reader>& b, int* window) {
+  uint32_t v;
+  if (!png_take(b, 16, &v)) return false;
+  const uint32_t cmf = v & 0xFF, flg = v >> 8;
+  if ((cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 || (flg & 0x20)) return false;
+  *window = 1 << ((cmf >> 4) + 8);
+  return true;
+}
+
+// The whole stream into `out` (see the sinks of sdsj_png.hip and tests/asan/png_driver.cpp):
+//   out.lit(byte)          appends one byte
+//   out.match(dist, len)   appends len bytes copied from dist bytes back (overlap allowed)
+// The sink never sees a byte beyond `expect` or a source before the first byte: both end the image
+// here.  Returns SDSJ_OK when the stream is well formed, ends in a final block and produced exactly
+// `expect` bytes; *adler = the trailer's value (the caller compares it with the output's).
+template <class Reader, class Sink>
+SDSJ_HDI int png_inflate(PngBits<Reader>& b, InfTables* T, Sink& out, int64_t expect, uint32_t* adler) {
+  int window = 0;
+  if (!zlib_header(b, &window)) return SDSJ_CORRUPT;
+  int64_t produced = 0;
+  for (;;) {
+    int final = 0, type = 0, stored = 0;
+    if (!inf_block_header(b, T, &final, &type, &stored)) return SDSJ_CORRUPT;
+    if (type == 0) {
+      if (produced + stored > expect) return SDSJ_CORRUPT;
+      for (int k = 0; k < stored; k++) {
+        uint32_t v;
+        if (!png_take(b, 8, &v)) return SDSJ_CORRUPT;
+        out.lit((int)v);
+      }
+      produced += stored;
+    } else {
+      for (;;) {
+        const int s = inf_decode(b, &T->ll, T->ll_sym);
+        if (s < 0) return SDSJ_CORRUPT;
+        if (s < 256) {
+          if (produced >= expect) return SDSJ_CORRUPT;
+          out.lit(s);
+          produced++;
+          continue;
+        }
+        if (s == 256) break;
+        int len = 0, dist = 0;
+        if (!inf_length(b, s, &len) || !inf_distance(b, T, &dist)) return SDSJ_CORRUPT;
+        if (!inf_match_ok(produced, expect, dist, len, window)) return SDSJ_CORRUPT;
+        out.match(dist, len);
+        produced += len;
+      }
+    }
+    if (final) break;
+  }
+  if (produced != expect) return SDSJ_CORRUPT;
+  const int drop = b.cnt & 7;
+  b.buf >>= drop;
+  b.cnt -= drop;
+  uint32_t v;
+  if (!png_take(b, 32, &v)) return SDSJ_CORRUPT;
+  *adler = ((v & 0xFF) << 24) | ((v & 0xFF00) << 8) | ((v >> 8) & 0xFF00) | (v >> 24);
+  if (!png_tail_ok(b)) return SDSJ_UNSUPPORTED;
+  return SDSJ_OK;
+}
+
+constexpr uint32_t kAdlerMod = 65521;
+
+// ------------------------------------------------------------------------------------------
+// Filters (PNG specification 9.2; ZipDecode.c).  Pixels travel as packed little-endian dwords of bpp
+// bytes: raw = the filtered bytes, a = left, b = up, c = up-left (zeros outside the image).
+// ------------------------------------------------------------------------------------------
+SDSJ_HD inline int png_paeth(int a, int b, int c) {
+  const int p = a + b - c;
+  const int pa = p > a ? p - a : a - p, pb = p > b ? p - b : b - p, pc = p > c ? p - c : c - p;
+  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+SDSJ_HD inline uint32_t png_recon(int ft, uint32_t raw, uint32_t a, uint32_t b, uint32_t c, int bpp) {
+  uint32_t r = 0;
+  for (int k = 0; k < bpp; k++) {
+    const int sh = 8 * k;
+    const int x = (int)((raw >> sh) & 255), pa = (int)((a >> sh) & 255), pb = (int)((b >> sh) & 255),
+              pc = (int)((c >> sh) & 255);
+    const int pred = ft == 0 ? 0 : ft == 1 ? pa : ft == 2 ? pb : ft == 3 ? ((pa + pb) >> 1) : png_paeth(pa, pb, pc);
+    r |= (uint32_t)((x + pred) & 255) << sh;
+  }
+  return r;
+}
+
+// The reconstructed pixel as convert("RGB") gives it: gray replicated, alpha dropped (no
+// premultiplication), palette entries looked up -- (0, 0, 0) at or beyond the PLTE length or without
+// a PLTE.  `pal(i)` returns palette byte i (3 per entry).  Returns r | g << 8 | b << 16.
+template <class Pal>
+SDSJ_HD inline uint32_t png_rgb(int ctype, uint32_t px, int plte_n, const Pal& pal) {
+  const uint32_t v = px & 255;
+  switch (ctype) {
+    case 0:
+    case 4:
+      return v | (v << 8) | (v << 16);
+    case 3:
+      if ((int)v >= plte_n) return 0;
+      return (uint32_t)pal(3 * (int)v) | ((uint32_t)pal(3 * (int)v + 1) << 8) | ((uint32_t)pal(3 * (int)v + 2) << 16);
+    default:
+      return px & 0xFFFFFFu;
+  }
+}
+
+// The descriptor of a parsed PNG: no components, blocks or entropy data, so every JPEG kernel that
+// walks all images of a batch finds nothing to do for it (they also test `png`).
+SDSJ_HD inline void png_fill_desc(ImgDesc* d, const PngHdr& h) {
+  d->width = h.width;
+  d->height = h.height;
+  d->ncomp = 0;
+  d->hmax = d->vmax = 1;
+  d->mcux = d->mcuy = d->bpm = 0;
+  d->restart_interval = 0;
+  d->nseg = 1;
+  d->saw_jfif = d->saw_adobe = d->adobe_transform = 0;
+  d->entropy_off = d->entropy_len = 0;
+  d->total_blocks = 0;
+  d->progressive = 0;
+  d->sos_pos = 0;
+  d->png = 1;
+  d->png_ctype = h.ctype;
+  d->png_bpp = h.bpp;
+  d->png_plte_n = h.plte_n;
+  d->png_plte_pos = h.plte_pos;
+  d->png_idat_pos = h.idat_pos;
+  d->png_raw = png_raw_bytes(h.width, h.height, h.bpp);
+  d->off_png = 0;
+}
+
+}  // namespace sdsj

@@ -148,6 +148,7 @@ class JpegEngine:
         self._pid = os.getpid()
         self._inflight: dict[int, tuple[torch.Tensor, int]] = {}
         self._fallback = 0  # samples the transforms decoded with PIL on the host (counters()["fallback"])
+        self._formats = _lib.FORMAT_JPEG  # the native engine's current mask (sdsj_engine_set_formats)
 
     # -- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -167,6 +168,15 @@ class JpegEngine:
             raise RuntimeError(f"{what} failed ({_lib.STATUS_NAMES.get(rc, rc)}): {err.decode() if err else ''}")
 
     # -- helpers ---------------------------------------------------------------------------
+    def _set_formats(self, formats) -> None:
+        """``formats``: a tuple of "jpeg" / "png", or None for the default (JPEG only).  The per-process
+        engine is shared between transforms, so the mask travels with every call: the native mask is
+        changed only when this call's differs from the one in force."""
+        mask = _lib.format_mask(formats)
+        if mask != self._formats:
+            self._check(self.lib.sdsj_engine_set_formats(self._h, mask), "sdsj_engine_set_formats")
+            self._formats = mask
+
     @staticmethod
     def make_op(resolution, crop_before_resize=True, filter="bilinear", normalize=False, layout="chw") -> SdsjOp:
         out_h, out_w = (int(v) for v in resolution)
@@ -210,9 +220,11 @@ class JpegEngine:
     # -- host-bytes batch ------------------------------------------------------------------
     def decode_resize(self, jpgs: Sequence[bytes], resolution, *, crop_before_resize: bool = True,
                       filter: str = "bilinear", normalize: bool = False, flip: Optional[Sequence[bool]] = None,
-                      layout: str = "chw", out: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, np.ndarray]:
+                      layout: str = "chw", out: Optional[torch.Tensor] = None,
+                      formats=None) -> tuple[torch.Tensor, np.ndarray]:
         """Decodes host JPEG bytes (a list of bytes, or an EncodedBatch) into a [n, 3, H, W] (or
-        [n, H, W, 3]) device tensor.
+        [n, H, W, 3]) device tensor.  ``formats``: the sample formats decoded natively, a tuple of "jpeg"
+        / "png" (None: JPEG only, PNG samples report UNSUPPORTED); see include/sdsj.h for the PNG subset.
 
         Returns (tensor, per-sample status array).  Failed samples are zero-filled; use
         ``raise_for_status`` to turn a status into the reference's OSError semantics.
@@ -229,6 +241,7 @@ class JpegEngine:
         if n == 0:
             return out, np.zeros(0, np.int32)
         ptrs, lens, _keep = _c_samples(jpgs)
+        self._set_formats(formats)
         flip_arr = None
         if flip is not None:
             flip_arr = (ctypes.c_uint8 * n)(*[1 if f else 0 for f in flip])
@@ -243,7 +256,7 @@ class JpegEngine:
     # -- asynchronous host path ----------------------------------------
     def submit(self, slot: int, samples: Sequence, resolution, *, files: bool = False, crop_before_resize: bool = True,
                filter: str = "bilinear", normalize: bool = False, flip: Optional[Sequence[bool]] = None,
-               layout: str = "chw", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               layout: str = "chw", out: Optional[torch.Tensor] = None, formats=None) -> torch.Tensor:
         """Stages a batch into pinned slot ``slot`` (0 or 1) and enqueues H2D + decode without waiting.
 
         ``samples``: encoded bytes (a list, or an EncodedBatch), or file paths with ``files=True`` (read straight into the pinned
@@ -263,6 +276,7 @@ class JpegEngine:
         if slot not in range(_lib.SLOTS):
             raise ValueError(f"slot must be in [0, {_lib.SLOTS})")
         flip_arr = (ctypes.c_uint8 * max(n, 1))(*[1 if f else 0 for f in flip]) if flip is not None else None
+        self._set_formats(formats)  # (the batch is parsed and planned under the mask in force at submit)
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             fl = ctypes.cast(flip_arr, ctypes.c_void_p) if flip_arr else None
@@ -290,7 +304,7 @@ class JpegEngine:
     def decode_stream(self, batches, resolution, *, files: bool = False, **kw):
         """Yields (out, status) per batch of ``batches`` (each a list of bytes, or of paths with
         ``files=True``), keeping one batch in flight: batch k + 1 is staged and copied while batch k
-        decodes (double-buffered pinned slots)."""
+        decodes (double-buffered pinned slots).  Keywords (``formats`` among them) go to ``submit``."""
         k, prev = 0, None
         for batch in batches:
             slot = k % _lib.SLOTS
@@ -306,7 +320,7 @@ class JpegEngine:
                              crop_before_resize: bool = True, filter: str = "bilinear", normalize: bool = False,
                              flip: Optional[torch.Tensor] = None, layout: str = "chw",
                              out: Optional[torch.Tensor] = None,
-                             status: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+                             status: Optional[torch.Tensor] = None, formats=None) -> tuple[torch.Tensor, torch.Tensor]:
         """Decodes JPEGs already resident in device memory (uint8 ``blob``; int64 ``offsets`` and
         int32 ``lengths`` per sample, both on the device).  Fully asynchronous on the current stream."""
         op = self.make_op(resolution, crop_before_resize, filter, normalize, layout)
@@ -326,6 +340,7 @@ class JpegEngine:
             self._check_dev(status, "status", torch.int32, n)
         if flip is not None:
             self._check_dev(flip, "flip", torch.uint8, n)
+        self._set_formats(formats)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = self.lib.sdsj_decode_resize_batch_device(
@@ -394,13 +409,15 @@ class JpegEngine:
 
     @staticmethod
     def scratch_need(jpgs: Sequence[bytes], resolution, *, crop_before_resize: bool = True, filter: str = "bilinear",
-                     normalize: bool = False, layout: str = "chw") -> int:
-        """Device scratch bytes a batch of these JPEGs needs (host planning, sdsj_plan_need): what
-        ``reserve`` must provide before ``decode_resize_device`` decodes them in one call."""
+                     normalize: bool = False, layout: str = "chw", formats=None) -> int:
+        """Device scratch bytes a batch of these samples needs (host planning, sdsj_plan_need_formats): what
+        ``reserve`` must provide before ``decode_resize_device`` decodes them in one call with the same
+        ``formats``."""
         op = JpegEngine.make_op(resolution, crop_before_resize, filter, normalize, layout)
         lib, tot, need = _lib.load(), 0, ctypes.c_int64()
+        mask = _lib.format_mask(formats)
         for j in jpgs:
-            lib.sdsj_plan_need(j, len(j), ctypes.byref(op), ctypes.byref(need))
+            lib.sdsj_plan_need_formats(j, len(j), ctypes.byref(op), mask, ctypes.byref(need))
             tot += need.value
         return tot
 

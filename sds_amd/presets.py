@@ -192,11 +192,20 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     the DataLoader workers -- which get host tensors (the reference's type; pin_memory pins them) and
     never initialise HIP themselves.  ``None`` = every process creates its own engine (device outputs,
     reaching the parent through HIP IPC); a string = the address of a running service.
+
+    ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` /
+    ``"png"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
+    every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
+    exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
+    is meant for batched use (GpuDecodeBatch): a single-image call has a longer latency than PIL's decode.
+    In a served worker process (the decode service) PNG samples keep the PIL route whatever this says: the
+    service's wire protocol carries no format mask.
     """
 
     def __init__(self, input_field: str, output_field: Optional[str] = None, resolution=(256, 256),
                  normalize: bool = False, device=None, hflip_prob: float = 0.0, output_device=None,
-                 service="auto", **resize_kwargs):
+                 service="auto", gpu_formats=("jpeg",), **resize_kwargs):
         super().__init__(input_field, output_field)
         self.output_device = None if output_device is None else torch.device(output_device)
         self.resolution = tuple(int(v) for v in resolution)
@@ -208,9 +217,15 @@ class GpuDecodeResizeImageTransform(BaseTransform):
         F.check_resize_kwargs(self.resize_kwargs)
         self._owner_pid = os.getpid()
         self.service_address = _service_address(service, device)
+        self.gpu_formats = tuple(gpu_formats)
+        _lib.format_mask(self.gpu_formats)  # (rejects unknown names here, not at the first sample)
 
     def __getstate__(self):
         return dict(self.__dict__)  # no native handle is ever stored on the transform
+
+    def _formats_kw(self) -> dict:
+        # (nothing for the default: the engine call's own default is JPEG only)
+        return {} if self.gpu_formats == ("jpeg",) else {"formats": self.gpu_formats}
 
     def _served(self) -> bool:
         return self.service_address is not None and os.getpid() != self._owner_pid
@@ -229,7 +244,10 @@ class GpuDecodeResizeImageTransform(BaseTransform):
         # again, after PIL's decode, as the reference does) leaves the RNGs one draw ahead, not two
         rng = _RngSnapshot(kw.get("random_resize") is not None, self.hflip_prob > 0.0)
         if need_size:
-            st, info = _lib.probe(data)
+            if eng is not None and "png" in self.gpu_formats and data[:8] == _lib.PNG_SIGNATURE:
+                st, info = _lib.png_probe(data)
+            else:
+                st, info = _lib.probe(data)
             if st != _lib.OK or info.width <= 0 or info.height <= 0:  # not a JPEG this path decodes
                 img = self._host(eng, data)
                 sample[self.output_field] = img.permute(2, 0, 1)
@@ -245,7 +263,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
         else:
             out, status = eng.decode_resize([data], resolution, crop_before_resize=kw.get("crop_before_resize", True),
                                             filter=F.filter_name(kw.get("interpolation_mode", "bilinear")),
-                                            normalize=self.normalize, flip=flip, layout="hwc")
+                                            normalize=self.normalize, flip=flip, layout="hwc", **self._formats_kw())
             st = int(status[0])
             img = out[0]
         if st in (_lib.UNSUPPORTED, _lib.CORRUPT):
@@ -516,9 +534,11 @@ def create_standard_image_pipeline(
     hflip_prob: float = 0.0,
     output_device=None,
     service="auto",
+    gpu_formats=("jpeg",),
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
-    see GpuDecodeResizeImageTransform (the decode service for DataLoader workers).
+    see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
+    formats decoded natively (add ``"png"`` to opt in; see GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
     the pipeline gets device tensors (it decodes in-process), while its forked DataLoader workers get
@@ -531,7 +551,8 @@ def create_standard_image_pipeline(
         LoadFromDiskTransform([image_field]),
         GpuDecodeResizeImageTransform(input_field=image_field, output_field=output_field, resolution=resolution,
                                       normalize=normalize, device=device, hflip_prob=hflip_prob,
-                                      output_device=output_device, service=service, **resize_kwargs),
+                                      output_device=output_device, service=service, gpu_formats=gpu_formats,
+                                      **resize_kwargs),
     ]
     if return_image_as_single_frame_video:
         transforms.extend([
