@@ -118,7 +118,8 @@ int sdsj_png_probe(const uint8_t* png, size_t n, sdsj_png_info* out);
  * has SDSJ_FORMAT_PNG (a format outside the mask reports SDSJ_UNSUPPORTED, need 0). */
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need);
 
-/* Creates an engine bound to HIP device `hip_device`.  Scratch memory is owned by the engine. */
+/* Creates an engine bound to HIP device `hip_device`.  Scratch memory is owned by the engine.  An engine
+ * takes one host call at a time: callers with several threads use one engine each, as the decode service does. */
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out);
 int sdsj_engine_destroy(sdsj_engine* eng);
 

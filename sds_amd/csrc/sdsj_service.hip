@@ -43,11 +43,14 @@
 #include <vector>
 
 #include "sdsj.h"
+#include "sdsj_buffers.h"
 
 namespace {
 
 static_assert(sizeof(sdsj_svc_req) == 72, "wire format");
 static_assert(sizeof(sdsj_svc_rep) == 16, "wire format");
+
+using namespace sdsj;
 
 volatile sig_atomic_t g_stop = 0;
 void on_signal(int) { g_stop = 1; }
@@ -137,9 +140,9 @@ class Service {
     lanes_.resize(nl);
     for (auto& l : lanes_) {
       sdsj_cfg ec{SDSJ_ABI_VERSION, max_batch_, 0};
-      if (sdsj_engine_create(cfg_.device, &ec, &l.e) != SDSJ_OK) return fail("sdsj_engine_create", SDSJ_EHIP);
-      if (hipStreamCreateWithFlags(&l.s, hipStreamNonBlocking) != hipSuccess) return fail("stream", SDSJ_EHIP);
-      if (hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess) return fail("event", SDSJ_EHIP);
+      if (sdsj_engine_create(cfg_.device, &ec, l.e.put()) != SDSJ_OK) return fail("sdsj_engine_create", SDSJ_EHIP);
+      if (hipStreamCreateWithFlags(l.s.put(), hipStreamNonBlocking) != hipSuccess) return fail("stream", SDSJ_EHIP);
+      if (hipEventCreateWithFlags(l.done.put(), hipEventDisableTiming) != hipSuccess) return fail("event", SDSJ_EHIP);
       l.status.resize(max_batch_);
     }
     ep_ = epoll_create1(EPOLL_CLOEXEC);
@@ -182,18 +185,19 @@ class Service {
   }
 
  private:
-  struct Lane {  // one engine, its stream, and the batch it runs
-    sdsj_engine* e = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t done = nullptr;
-    uint8_t* d_out = nullptr;
-    uint8_t* h_out = nullptr;  // pinned
-    size_t out_cap = 0;
+  struct EngineDestroy {
+    static void destroy(sdsj_engine* e) { (void)sdsj_engine_destroy(e); }
+  };
+  struct Lane {  // one engine, its stream, and the batch it runs (members are released last to first)
+    Handle<sdsj_engine*, EngineDestroy> e;
+    Stream s;
+    Event done;
+    DeviceBuf<uint8_t> d_out;
+    PinnedBuf<uint8_t> h_out;  // (same size as d_out)
     std::vector<Req> batch;
     std::vector<int32_t> status;
     // frame path buffers (grow only)
-    uint8_t *fr_in = nullptr, *fr_out = nullptr, *fr_small = nullptr;
-    size_t fr_in_cap = 0, fr_out_cap = 0;
+    DeviceBuf<uint8_t> fr_in, fr_out, fr_small;
   };
 
   int fail(const char* what, int code) {
@@ -205,15 +209,7 @@ class Service {
   void shutdown() {
     for (auto& kv : clients_) drop(*kv.second);
     clients_.clear();
-    for (auto& l : lanes_) {
-      if (l.e) sdsj_engine_destroy(l.e);
-      if (l.s) (void)hipStreamDestroy(l.s);
-      if (l.done) (void)hipEventDestroy(l.done);
-      (void)hipFree(l.d_out);
-      (void)hipHostFree(l.h_out);
-      (void)hipFree(l.fr_in), (void)hipFree(l.fr_out), (void)hipFree(l.fr_small);
-      l = Lane();
-    }
+    lanes_.clear();
     if (ep_ >= 0) close(ep_);
     ep_ = -1;
   }
@@ -349,15 +345,12 @@ class Service {
     const sdsj_op op = l.batch[0].r.op;
     const int64_t ob = out_bytes(op);
     const size_t need = (size_t)ob * n;
+    const hipStream_t s = l.s.get();
     int rc = SDSJ_OK;
-    if (need > l.out_cap) {
-      (void)hipFree(l.d_out);
-      (void)hipHostFree(l.h_out);
-      l.d_out = l.h_out = nullptr;
-      l.out_cap = 0;
+    if (need > l.h_out.size()) {
       const size_t cap = std::max(need, (size_t)ob * max_batch_ / 4);
-      if (hipMalloc(&l.d_out, cap) != hipSuccess || hipHostMalloc(&l.h_out, cap) != hipSuccess) rc = SDSJ_ENOMEM;
-      else l.out_cap = cap;
+      l.h_out.reset();  // (the check above reads h_out: empty unless both were allocated)
+      if (!l.d_out.reserve(cap) || !l.h_out.reserve(cap)) rc = SDSJ_ENOMEM;
     }
     std::vector<const uint8_t*> ptrs(n);
     std::vector<size_t> lens(n);
@@ -370,18 +363,18 @@ class Service {
     // everything on the lane's one stream (H2D, kernels, status), so the lanes' streams are the only
     // ones the service queues work on: one hardware queue each
     if (rc == SDSJ_OK)
-      rc = sdsj_decode_resize_batch(l.e, n, ptrs.data(), lens.data(), &op, flips.data(), l.d_out, l.status.data(), l.s);
+      rc = sdsj_decode_resize_batch(l.e.get(), n, ptrs.data(), lens.data(), &op, flips.data(), l.d_out.get(), l.status.data(), s);
     const double t1 = trace_ ? now_us() : 0;
-    if (rc == SDSJ_OK && hipMemcpyAsync(l.h_out, l.d_out, need, hipMemcpyDeviceToHost, l.s) != hipSuccess) rc = SDSJ_EHIP;
-    if (rc == SDSJ_OK && hipStreamSynchronize(l.s) != hipSuccess) rc = SDSJ_EHIP;
+    if (rc == SDSJ_OK && hipMemcpyAsync(l.h_out.get(), l.d_out.get(), need, hipMemcpyDeviceToHost, s) != hipSuccess) rc = SDSJ_EHIP;
+    if (rc == SDSJ_OK && hipStreamSynchronize(s) != hipSuccess) rc = SDSJ_EHIP;
     if (rc != SDSJ_OK) {
-      log_err("batch", sdsj_last_error(l.e));
-      (void)hipStreamSynchronize(l.s);
+      log_err("batch", sdsj_last_error(l.e.get()));
+      (void)hipStreamSynchronize(s);
       std::fill(l.status.begin(), l.status.begin() + n, rc);
     }
     for (int i = 0; i < n; i++) {
       Req& q = l.batch[i];
-      if (!q.c->closed.load() && l.status[i] == SDSJ_OK) memcpy(q.c->base + q.r.out_off, l.h_out + (size_t)i * ob, ob);
+      if (!q.c->closed.load() && l.status[i] == SDSJ_OK) memcpy(q.c->base + q.r.out_off, l.h_out.get() + (size_t)i * ob, ob);
       q.c->reply(q.r.seq, l.status[i]);
       q.c->release();
     }
@@ -395,27 +388,24 @@ class Service {
   int run_frame(Lane& l, Client& c, const sdsj_svc_req& r) {
     const int64_t fb = (int64_t)r.width * r.height * 3;
     const int64_t ob = out_bytes(r.op);
-    if ((size_t)fb > l.fr_in_cap || (size_t)ob > l.fr_out_cap || !l.fr_small) {
-      (void)hipFree(l.fr_in), (void)hipFree(l.fr_out), (void)hipFree(l.fr_small);
-      l.fr_in = l.fr_out = l.fr_small = nullptr;
-      l.fr_in_cap = l.fr_out_cap = 0;
-      if (hipMalloc(&l.fr_in, fb) != hipSuccess || hipMalloc(&l.fr_out, ob) != hipSuccess || hipMalloc(&l.fr_small, 16) != hipSuccess)
-        return SDSJ_ENOMEM;
-      l.fr_in_cap = (size_t)fb;
-      l.fr_out_cap = (size_t)ob;
+    if ((size_t)fb > l.fr_in.size() || (size_t)ob > l.fr_out.size() || !l.fr_small) {
+      l.fr_small.reset();  // (a failure part way leaves fr_small empty: the next frame allocates again)
+      if (!l.fr_in.reserve(fb) || !l.fr_out.reserve(ob) || !l.fr_small.reserve(16)) return SDSJ_ENOMEM;
     }
     // fr_small: [0, 4) the frame's status, [4] its flip flag
+    const hipStream_t s = l.s.get();
+    uint8_t *fr_in = l.fr_in.get(), *fr_out = l.fr_out.get(), *fr_small = l.fr_small.get();
     uint8_t small[8] = {0, 0, 0, 0, (uint8_t)(r.flip ? 1 : 0), 0, 0, 0};
-    if (hipMemcpyAsync(l.fr_in, c.base, fb, hipMemcpyHostToDevice, l.s) != hipSuccess ||
-        hipMemcpyAsync(l.fr_small, small, sizeof(small), hipMemcpyHostToDevice, l.s) != hipSuccess ||
-        hipStreamSynchronize(l.s) != hipSuccess)
+    if (hipMemcpyAsync(fr_in, c.base, fb, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(fr_small, small, sizeof(small), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
       return SDSJ_EHIP;
-    int st = sdsj_resize_frames_device(l.e, 1, l.fr_in, r.width, r.height, fb, &r.op, l.fr_small + 4, l.fr_out,
-                                       reinterpret_cast<int32_t*>(l.fr_small), l.s);
+    int st = sdsj_resize_frames_device(l.e.get(), 1, fr_in, r.width, r.height, fb, &r.op, fr_small + 4, fr_out,
+                                       reinterpret_cast<int32_t*>(fr_small), s);
     if (st != SDSJ_OK) return st;
-    if (hipMemcpyAsync(small, l.fr_small, sizeof(small), hipMemcpyDeviceToHost, l.s) != hipSuccess ||
-        hipMemcpyAsync(c.base + r.out_off, l.fr_out, ob, hipMemcpyDeviceToHost, l.s) != hipSuccess ||
-        hipStreamSynchronize(l.s) != hipSuccess)
+    if (hipMemcpyAsync(small, fr_small, sizeof(small), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(c.base + r.out_off, fr_out, ob, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
       return SDSJ_EHIP;
     int32_t fst;
     memcpy(&fst, small, sizeof(fst));
