@@ -40,7 +40,9 @@ class ImgDescC(ctypes.Structure):
                 ("progressive", i32), ("lat", i32), ("sos_pos", i64), ("off_ptab", i64),
                 ("off_tiles", i64), ("ntiles", i32), ("rs_lay", i32), ("plan_base", i64),
                 ("smooth", i32), ("sm_good", i32), ("sm_bits", ctypes.c_int8 * 60), ("mh", ctypes.c_int8),
-                ("sm_pad", ctypes.c_int8 * 3), ("etab", i32), ("etab_pad", i32)]
+                ("sm_pad", ctypes.c_int8 * 3), ("etab", i32), ("etab_pad", i32),
+                ("png", i32), ("png_ctype", i32), ("png_bpp", i32), ("png_plte_n", i32),
+                ("png_plte_pos", i64), ("png_idat_pos", i64), ("png_raw", i64), ("off_png", i64)]
 
 
 def _memcpy_d2h(ptr: int, nbytes: int) -> np.ndarray:
