@@ -33,6 +33,7 @@
 #include "sdsj_buffers.h"
 #include "sdsj_common.h"
 #include "sdsj_kernels.h"
+#include "sdsj_plan.h"
 #include "sdsj_stage_pool.h"
 
 using namespace sdsj;
@@ -640,18 +641,12 @@ int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out) {
   memset(out, 0, sizeof(*out));
   ImgDesc d;
   static thread_local ImgTables t;
-  struct R {
-    const uint8_t* p;
-    int operator()(int64_t i) const { return p[i]; }
-  } rd{jpg};
-  int st = parse_headers(rd, (int64_t)n, &d, &t, CopySink<R>{rd});
+  MemReader rd{jpg};
+  int st = parse_sample(rd, (int64_t)n, &d, &t, CopySink<MemReader>{rd});
   out->width = d.width;
   out->height = d.height;
   out->ncomp = d.ncomp;
-  if (st == SDSJ_OK) st = setup_geometry(&d, &t);
-  for (int c = 0; st == SDSJ_OK && !d.progressive && c < d.ncomp; c++)  // (progressive: checked per scan)
-    if (!huff_table_ok(t.dc_spec[d.comp[c].td], true) || !huff_table_ok(t.ac_spec[d.comp[c].ta], false))
-      st = SDSJ_CORRUPT;
+  if (st == SDSJ_OK && !scan_tables_ok(d, t)) st = SDSJ_CORRUPT;
   for (int c = 0; c < d.ncomp && c < 3; c++) {
     out->h_samp[c] = d.comp[c].h;
     out->v_samp[c] = d.comp[c].v;

@@ -1,0 +1,205 @@
+// sdsj_idct.hip -- gfx950 (MI355X) kernel of the inverse DCT (its arithmetic: sdsj_idct.h).
+//
+// Stage map (reference behaviour each kernel reproduces, see DESIGN.md for the layout/rooflines):
+//   k_idct     dequant + ISLOW IDCT                jidctint.c jpeg_idct_islow
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sdsj_common.h"
+#include "sdsj_kernels.h"
+#include "sdsj_idct.h"
+
+#pragma clang fp contract(off)
+
+namespace sdsj {
+
+// ------------------------------------------------------------------------------------------
+// k_idct: dequantisation + ISLOW IDCT with the SIMD version's 16-bit semantics (sdsj_idct.h); one block per
+// thread, 256 blocks per iteration.
+// ------------------------------------------------------------------------------------------
+constexpr int kIdctThreads = 256;
+#ifndef SDSJ_IDCT_GRID
+#define SDSJ_IDCT_GRID 8
+#endif
+constexpr int kIdctGrid = SDSJ_IDCT_GRID;  // workgroups per image (each strides over 8-block groups)
+// SDSJ_IDCT_GPW > 0 (0: kIdctGrid per image): batch launches take kIdctGridMax workgroups per image and an image uses
+// ceil(total_blocks / 8 / SDSJ_IDCT_GPW) of them (1 .. kIdctGridMax; the rest exit at once), so a
+// workgroup's setup is amortised over about the same number of groups whatever the image size.
+#ifndef SDSJ_IDCT_GPW
+#define SDSJ_IDCT_GPW 256
+#endif
+// (odd: workgroup k of the launch runs on XCD k mod 8, so with a grid row of 16 every image's first
+// workgroups would land on the same XCDs; 17 rotates them by one XCD per image)
+constexpr int kIdctGridMax = 17;
+
+// Work unit = a group: 8 horizontally adjacent blocks of one component, one per thread, so each of
+// a block's 8 row stores joins the group's other 7 in 64 contiguous bytes of a plane row.  The
+// block stays in registers through both passes (64 values), so there is no LDS transpose.
+#ifndef SDSJ_IDCT_WAVES
+#define SDSJ_IDCT_WAVES 4  // waves per SIMD the register budget targets (124 VGPRs at 4)
+#endif
+__global__ void __launch_bounds__(kIdctThreads) __attribute__((amdgpu_waves_per_eu(SDSJ_IDCT_WAVES)))
+k_idct(int n, const ImgDesc* __restrict__ descs,
+                                                       const ImgTables* __restrict__ tables,
+                                                       uint8_t* __restrict__ scratch) {
+  const int img = blockIdx.y;
+  if (img >= n) return;
+  const ImgDesc* d = &descs[img];
+  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->png) return;
+  int nwg = gridDim.x;  // this image's workgroups
+  if (SDSJ_IDCT_GPW > 0 && gridDim.x == kIdctGridMax) {
+    const int64_t want = ((int64_t)d->total_blocks / 8 + SDSJ_IDCT_GPW - 1) / SDSJ_IDCT_GPW;
+    nwg = want < 1 ? 1 : (want > kIdctGridMax ? kIdctGridMax : (int)want);
+    if ((int)blockIdx.x >= nwg) return;
+  }
+  __shared__ alignas(16) int32_t qt[kMaxComp][64];
+  __shared__ int32_t binv[kMaxComp][16];  // (dy * 4 + dx) -> MCU block index b (jdcoefct order)
+  __shared__ int32_t gstart[kMaxComp + 1], ngx[kMaxComp], cbw[kMaxComp], ch_[kMaxComp], cv_[kMaxComp], cpitch[kMaxComp];
+  __shared__ int32_t cgx0[kMaxComp], cby0[kMaxComp];  // first 8-block group column / block row needed
+  __shared__ float rngx[kMaxComp], rch[kMaxComp], rcv[kMaxComp];  // reciprocals for the exact quotients below
+  __shared__ int64_t cplane[kMaxComp];
+  const int t = threadIdx.x;
+  const int ncomp = d->ncomp, bpm = d->bpm, mcux = d->mcux;
+  // quantisation tables in zigzag order (the coefficient blocks' order)
+  for (int i = t; i < ncomp * 64; i += kIdctThreads) qt[i / 64][i % 64] = tables[img].qt[d->comp[i / 64].tq][natural_order(i % 64)];
+  if (t < bpm) binv[d->blk_comp[t]][d->blk_dy[t] * 4 + d->blk_dx[t]] = t;
+  if (t == 0) {
+    // only the blocks whose pixels the colour/resample passes read (comp_block_rect: the crop's source
+    // rectangle widened by one sample), in groups of 8 horizontally adjacent blocks aligned to 8 block
+    // columns, so each group's row stores fill whole 64-byte plane segments (groups starting at the
+    // first needed block column instead: k_idct 4.70 -> 5.18 ms per 16,384, profiles/r05_ab.txt)
+    int acc = 0;
+    for (int c = 0; c < ncomp; c++) {
+      const CompDesc& cd = d->comp[c];
+      int bx0, bx1, by0, by1;
+      const bool any = comp_block_rect(*d, c, bx0, bx1, by0, by1);
+      gstart[c] = acc;
+      cgx0[c] = bx0 >> 3;
+      ngx[c] = (bx1 >> 3) - cgx0[c] + 1;
+      cby0[c] = by0;
+      cbw[c] = cd.bw;
+      ch_[c] = ncomp == 1 ? 1 : cd.h;
+      cv_[c] = ncomp == 1 ? 1 : cd.v;
+      cpitch[c] = cd.pitch;
+      cplane[c] = cd.plane_off;
+      rngx[c] = 1.0f / (float)ngx[c];
+      rch[c] = 1.0f / (float)ch_[c];
+      rcv[c] = 1.0f / (float)cv_[c];
+      acc += any ? ngx[c] * (by1 - by0 + 1) : 0;
+    }
+    gstart[ncomp] = acc;
+  }
+  __syncthreads();
+  const int lb = t & 7;  // this lane's block within its group
+  const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + d->off_coef);
+  uint8_t* planes = scratch + d->off_planes;
+  const int ngroups = gstart[ncomp];
+  // blocks the entropy decoder left zero (jdhuff.c insufficient_data): from vend[k] to the end of
+  // restart interval k, and all of an empty interval entered out of data
+  const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
+  const int nseg = d->nseg;
+  const int bps = d->restart_interval ? d->restart_interval * bpm : (int)d->total_blocks;
+  const int vend0 = d->progressive ? 0 : sv.vend[0];
+  const bool prog = d->progressive != 0;  // (k_prog decodes every block; no cut intervals)
+  auto zero_block = [&](int g) {
+    if (prog) return false;
+    if (nseg == 1) return g >= vend0;
+    const int k = g / bps;
+    return g >= sv.vend[k] || (k > 0 && (sv.flag[k] & kSegEmpty) && (sv.flag[k - 1] & kSegIns));
+  };
+  // a / b for 0 <= a < 2^22, 1 <= b: float estimate, then one correction each way (exact)
+  auto qdiv = [](int a, int b, float rb) {
+    int q = (int)((float)a * rb);
+    q -= q * b > a ? 1 : 0;
+    q += (q + 1) * b <= a ? 1 : 0;
+    return q;
+  };
+  // block lb of group grp: component, block coordinates, decode-order index (g < 0: none)
+  auto locate = [&](int grp, int& c, int& by, int& bx, int& g) {
+    c = ncomp > 1 && grp >= gstart[1] ? (ncomp > 2 && grp >= gstart[2] ? 2 : 1) : 0;
+    const int local = grp - gstart[c];
+    const int byl = qdiv(local, ngx[c], rngx[c]);
+    by = cby0[c] + byl;
+    bx = (cgx0[c] + local - byl * ngx[c]) * 8 + lb;
+    g = -1;
+    if (grp < ngroups && bx < cbw[c]) {
+      const int h = ch_[c], v = cv_[c];
+      const int mx = qdiv(bx, h, rch[c]), my = qdiv(by, v, rcv[c]);
+      g = (my * mcux + mx) * bpm + binv[c][(by - my * v) * 4 + (bx - mx * h)];
+    }
+  };
+  // One block per lane, held in registers: dequantise, columns (pass 1), rows (pass 2), each row's 8
+  // bytes stored straight to the plane -- no LDS transposes.  The 8 lanes of a group write 64
+  // contiguous bytes of a plane row per store.
+  for (int grp = blockIdx.x * (kIdctThreads / 8) + (t >> 3); grp < ngroups; grp += nwg * (kIdctThreads / 8)) {
+    int c, by, bx, g;
+    locate(grp, c, by, bx, g);
+    if (g < 0) continue;
+    // the block (zigzag order, k_entwrite / k_prog), or zeros where the entropy decoder left it zero
+    const uint4* src = reinterpret_cast<const uint4*>(coef + (int64_t)g * 64);
+    const bool zb = zero_block(g);
+    uint4 raw[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) raw[i] = zb ? make_uint4(0, 0, 0, 0) : src[i];
+    // `ac`: any raw coefficient outside row 0 (the SIMD pass 1's zero test); row 0 is zigzag positions
+    // 0, 1, 5, 6, 14, 15, 27 and 28
+    uint32_t ac = raw[0].y | (raw[0].z & 0xFFFFu) | (raw[0].w & 0xFFFF0000u) | raw[1].x | raw[1].y | raw[1].z |
+                  raw[3].x | (raw[3].y & 0xFFFFu) | (raw[3].z & 0xFFFF0000u) | raw[3].w;
+#pragma unroll
+    for (int i = 2; i < 8; i++) ac |= i == 3 ? 0u : (raw[i].x | raw[i].y | raw[i].z | raw[i].w);
+    // DEQUANTIZE as vpmullw: the low 16 bits of coef * quantval, zigzag position k into row-major
+    // natural_order(k)
+    int x[64];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const int4 q0 = *reinterpret_cast<const int4*>(&qt[c][i * 8]), q1 = *reinterpret_cast<const int4*>(&qt[c][i * 8 + 4]);
+      const uint32_t w[4] = {raw[i].x, raw[i].y, raw[i].z, raw[i].w};
+      const int q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const int cv = (int)(int16_t)((w[k >> 1] >> ((k & 1) * 16)) & 0xFFFF);
+        x[natural_order(i * 8 + k)] = wrap16(cv * q[k]);
+      }
+    }
+    // pass 1: columns.  A block whose rows 1..7 are all zero takes the SIMD shortcut (vpsllw: every
+    // column is the dequantised DC << PASS1_BITS, wrapped to 16 bits); otherwise every column runs the
+    // butterfly, saturated to 16 bits.  On such a block the butterfly of column k gives sat16(4 x[k]) in
+    // every row, so the shortcut is the butterfly on x[k] = wrap16(4 x[k]) / 4 (exact: a multiple of 4).
+    if (!ac) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) x[k] = wrap16(x[k] * 4) >> 2;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      uint32_t o[8];
+      islow_1d(x[k], x[8 + k], x[16 + k], x[24 + k], x[32 + k], x[40 + k], x[48 + k], x[56 + k], o);
+#pragma unroll
+      for (int j = 0; j < 8; j++) x[j * 8 + k] = descale_p1(o[j]);
+    }
+    // pass 2: rows -> 8 bytes of plane row by * 8 + r
+    uint8_t* dst = planes + cplane[c] + (int64_t)(by * 8) * cpitch[c] + bx * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      uint32_t o[8];
+      islow_1d(x[r * 8], x[r * 8 + 1], x[r * 8 + 2], x[r * 8 + 3], x[r * 8 + 4], x[r * 8 + 5], x[r * 8 + 6], x[r * 8 + 7], o);
+      uint32_t lo = 0, hi = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) lo |= descale_p2(o[k]) << (8 * k);
+#pragma unroll
+      for (int k = 0; k < 4; k++) hi |= descale_p2(o[k + 4]) << (8 * k);
+      *reinterpret_cast<uint2*>(dst + (int64_t)r * cpitch[c]) = make_uint2(lo, hi);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Host-side launchers (called by the engine; all asynchronous on `stream`).
+// ------------------------------------------------------------------------------------------
+hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s) {
+  // (a few images: more workgroups per image, for latency)
+  hipLaunchKernelGGL(k_idct, dim3(n <= kSmallBatch ? 8 * kIdctGrid : (SDSJ_IDCT_GPW > 0 ? kIdctGridMax : kIdctGrid), n), dim3(kIdctThreads), 0, s, n, descs,
+                     tables, scratch);
+  return hipGetLastError();
+}
+
+}  // namespace sdsj

@@ -1,4 +1,6 @@
-// sdsj_kernels.h -- launchers of the gfx950 kernels in sdsj_kernels.hip (engine-internal).
+// sdsj_kernels.h -- launchers of every stage file's gfx950 kernels (sdsj_plan.hip, sdsj_unstuff.hip,
+// sdsj_entropy.hip, sdsj_progressive.hip, sdsj_png.hip, sdsj_idct.hip, sdsj_unfused.hip, sdsj_resample.hip,
+// sdsj_resample420.hip) and host-side planning (sdsj_plan.hip); engine-internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,7 +73,8 @@ hipError_t launch_resample420(int n, const ImgDesc* descs, const sdsj_op& op, in
 // (a negative length: the sample is reported as EINVAL -- an unreadable file of the host path)
 hipError_t launch_finish(int n, ImgDesc* descs, const sdsj_op& op, void* out, int32_t* status, const float* lut,
                          const int32_t* lengths, unsigned long long* counters, hipStream_t s);
-// host-side planning (same code as k_parse): returns the scratch bytes image `jpg` needs, or < 0
+// host-side planning (plan_sample of sdsj_plan.h, as k_parse runs it, without k_parse's validation of the
+// Huffman tables): returns the scratch bytes image `jpg` needs (0 unless *status is SDSJ_OK)
 // *routes (optional): the routes the image takes (bits as in route masks; all of them when the host
 // parse fails, so the device's own verdict is never starved of a kernel)
 // small: the latency-mode plan of a chunk of at most kSmallBatch images (k_parse's `small`)

@@ -66,7 +66,7 @@ __device__ __forceinline__ void comp_rows(const CompDesc& c, int ya, int yb, int
   }
 }
 
-// up_sample() of sdsj_kernels.hip over staged rows; r0 = row i, r1 = neighbour row f, both indexed
+// up_sample() of sdsj_unfused.hip over staged rows; r0 = row i, r1 = neighbour row f, both indexed
 // by absolute component column.
 __device__ __forceinline__ int up_lds(const uint8_t* r0, const uint8_t* r1, int rh, int rv, int dw, int x, int y) {
   if (rh == 1 && rv == 1) return r0[x];

@@ -1,6 +1,6 @@
 // Host AddressSanitizer / UBSan driver of the shared JPEG header parser (sds_amd/csrc/sdsj_common.h,
-// the code sdsj_probe and the device k_parse run).  Reads records [u32 length][bytes] from the file
-// in argv[1] and prints one line per record: status width height ncomp bpm total_blocks.
+// through parse_sample and scan_tables_ok of sdsj_plan.h: the code sdsj_probe and the device k_parse
+// run).  Reads records [u32 length][bytes] from the file in argv[1] and prints one line per record: status width height ncomp bpm total_blocks.
 // Each input is copied into an exactly sized heap buffer, so any read past its end is reported.
 #include <stdio.h>
 #include <stdlib.h>
@@ -8,14 +8,9 @@
 
 #include <vector>
 
-#include "../../sds_amd/csrc/sdsj_common.h"
+#include "../../sds_amd/csrc/sdsj_plan.h"
 
 using namespace sdsj;
-
-struct Rd {
-  const uint8_t* p;
-  int operator()(int64_t i) const { return p[i]; }
-};
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
@@ -37,12 +32,9 @@ int main(int argc, char** argv) {
     pos += n;
     ImgDesc* d = new ImgDesc();
     ImgTables* t = new ImgTables();
-    Rd rd{buf};
-    int st = parse_headers(rd, (int64_t)n, d, t, CopySink<Rd>{rd});
-    if (st == SDSJ_OK) st = setup_geometry(d, t);
-    for (int c = 0; st == SDSJ_OK && !d->progressive && c < d->ncomp; c++)
-      if (!huff_table_ok(t->dc_spec[d->comp[c].td], true) || !huff_table_ok(t->ac_spec[d->comp[c].ta], false))
-        st = SDSJ_CORRUPT;
+    MemReader rd{buf};
+    int st = parse_sample(rd, (int64_t)n, d, t, CopySink<MemReader>{rd});
+    if (st == SDSJ_OK && !scan_tables_ok(*d, *t)) st = SDSJ_CORRUPT;
     if (st == SDSJ_OK) {
       int x0, y0, cw, ch;
       crop_box(d->width, d->height, 256, 256, &x0, &y0, &cw, &ch);

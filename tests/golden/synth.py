@@ -85,7 +85,7 @@ def has_fill_stuffing(jpg: bytes) -> bool:
     zero) inside its scan -- before the first marker that ends it (RSTn and codes below SOF0 do not).
     jdhuff.c's slow path reads it as one FF data byte; libjpeg-turbo's decode_mcu_fast takes it for a
     marker and leaves that MCU's fast-path coefficients under the slow path's, so the MI355X kernels
-    report such streams SDSJ_CORRUPT and the transforms rerun them on PIL (sdsj_kernels.hip us_classify)."""
+    report such streams SDSJ_CORRUPT and the transforms rerun them on PIL (sdsj_unstuff.hip us_classify)."""
     d, i, ri = jpg, 2, 0
     while i + 4 <= len(d) and d[i] == 0xFF:
         m, ln = d[i + 1], (d[i + 2] << 8) | d[i + 3]

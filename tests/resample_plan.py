@@ -3,8 +3,10 @@
 Restates, in Python doubles with the C code's operation order, what decides the resample kernel an image
 gets: ``setup_geometry``'s component sizes, ``crop_box``, ``resample_ksize`` and ``filter_support``
 (sds_amd/csrc/sdsj_common.h), the tile-halving loop and the ``rs_*`` limits of ``plan_image`` and
-``image_routes`` (sds_amd/csrc/sdsj_kernels.hip), the lane split of ``run_chunk``
+``image_routes`` (sds_amd/csrc/sdsj_plan.h), the lane split of ``run_chunk``
 (sds_amd/csrc/sdsj_engine.hip) and the strip height of ``launch_resample`` (sds_amd/csrc/sdsj_resample.hip).
+tests/test_plan_host.py compares it with the C++ planner on the CPU, tests/test_gpu_resample_routes.py with
+the device's descriptors.
 
     p = plan(600, 450, S422, Op(400, 300))
     p.route_name          # 'kRtF_422_5'  (kRtF + lay * 5 + (kt - 3) / 2: k_rs420<5, 4:2:2>)

@@ -10,36 +10,12 @@ import struct
 import subprocess
 import tempfile
 
-import numpy as np
 import pytest
 
-from tests import goldens as G
+from tests.parser_inputs import inputs as _inputs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DRIVER = os.path.join(HERE, "asan", "parse_driver.cpp")
-
-
-def _inputs():
-    out = []
-    rng = np.random.default_rng(5)
-    for case, jpg, _ in G.g1():
-        out.append(jpg)
-    for c in G.load_json("g5_edge.json")["cases"]:
-        import base64
-        out.append(base64.b64decode(c["jpg_b64"]))
-    muts = []
-    for jpg in out:
-        from oracle import oracle as O  # locates the entropy segment only (test infrastructure)
-        _, info = O.probe(jpg)
-        hdr_end = int(info.entropy_offset) or min(len(jpg), 700)
-        for k in range(0, hdr_end + 2):
-            muts.append(jpg[:k])
-        for _ in range(40):
-            b = bytearray(jpg)
-            p = int(rng.integers(0, hdr_end))
-            b[p] = int(rng.integers(0, 256))
-            muts.append(bytes(b))
-    return out + muts + [b"", b"\x89PNG\r\n\x1a\n" + b"\x00" * 32, b"\xff\xd8", b"\xff\xd8\xff"]
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
