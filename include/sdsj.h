@@ -100,9 +100,17 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * PIL.Image.open(...).convert("RGB") -- gray replicated, alpha dropped, tRNS ignored, palette indices
  * at or beyond the PLTE length black.  A PNG outside that subset (interlaced, other depths, APNG, chunks
  * this path does not know before the image data) reports SDSJ_UNSUPPORTED and a stream this path is
- * not sure PIL decodes to the same pixels SDSJ_CORRUPT; callers rerun both on PIL, as for JPEG. */
+ * not sure PIL decodes to the same pixels SDSJ_CORRUPT; callers rerun both on PIL, as for JPEG.
+ *
+ * SDSJ_FORMAT_PNG_EXT (valid only together with SDSJ_FORMAT_PNG, SDSJ_EINVAL otherwise) widens the subset:
+ * Adam7 interlace, every legal (colour type, bit depth) pair -- gray 1 / 2 / 4 scaled by 255 / 85 / 17,
+ * palette 1 / 2 / 4, gray 16 clipped to 255 (PIL opens it as I;16), the high byte of gray + alpha, RGB
+ * and RGBA 16 -- and, before the image data, eXIf and every ancillary chunk PIL has no handler for
+ * (tIME, bKGD, sBIT, private ones; CRC checked).  APNG, iCCP, zTXt and iTXt stay SDSJ_UNSUPPORTED.
+ * Without the bit nothing changes: those files report SDSJ_UNSUPPORTED. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
+#define SDSJ_FORMAT_PNG_EXT 4
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -114,6 +122,10 @@ typedef struct sdsj_png_info {
  * IHDR is readable, and the status k_parse would give the sample with SDSJ_FORMAT_PNG enabled. */
 int sdsj_png_probe(const uint8_t* png, size_t n, sdsj_png_info* out);
 
+/* The same for an engine whose format mask is `formats` (it must have SDSJ_FORMAT_PNG): with
+ * SDSJ_FORMAT_PNG_EXT the wider subset is `supported`; without it the result is sdsj_png_probe's. */
+int sdsj_png_probe_formats(const uint8_t* png, size_t n, int formats, sdsj_png_info* out);
+
 /* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
  * has SDSJ_FORMAT_PNG (a format outside the mask reports SDSJ_UNSUPPORTED, need 0). */
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need);
@@ -123,7 +135,7 @@ int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int 
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out);
 int sdsj_engine_destroy(sdsj_engine* eng);
 
-/* Sets the formats (SDSJ_FORMAT_* mask, at least one) the engine decodes in batches submitted after the
+/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG and PNG) the engine decodes in batches submitted after the
  * call, on every decode entry point: sdsj_decode_resize_batch, sdsj_decode_resize_batch_device,
  * sdsj_submit_batch, sdsj_submit_files (and so what sdsj_wait_batch reports).  Default: JPEG only. */
 int sdsj_engine_set_formats(sdsj_engine* eng, int mask);
@@ -195,7 +207,7 @@ int sdsj_resize_frames_device(sdsj_engine* eng, int n, const uint8_t* d_frames, 
 #define SDSJ_CTR_BYTES_OUT 7   /* output tensor bytes written (failed samples included: zeros) */
 #define SDSJ_CTR_FRAMES 8      /* raw frames resized (sdsj_resize_frames_device) */
 #define SDSJ_CTR_PROGRESSIVE 9 /* progressive JPEGs decoded */
-#define SDSJ_CTR_PNG 10        /* PNG samples decoded natively (SDSJ_FORMAT_PNG) */
+#define SDSJ_CTR_PNG 10        /* PNG samples decoded natively (SDSJ_FORMAT_PNG, SDSJ_FORMAT_PNG_EXT) */
 #define SDSJ_NUM_COUNTERS 11
 int sdsj_engine_counters(sdsj_engine* eng, uint64_t* out, int cap, int reset);
 const char* sdsj_counter_name(int k);

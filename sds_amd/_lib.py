@@ -34,16 +34,18 @@ EXPORTS = [
     "sdsj_stage_name", "sdsj_engine_debug_buffers", "sdsj_resize_frames_device", "sdsj_submit_batch",
     "sdsj_submit_files", "sdsj_wait_batch", "sdsj_engine_counters", "sdsj_counter_name", "sdsj_engine_set_lanes",
     "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve", "sdsj_engine_set_formats", "sdsj_png_probe",
-    "sdsj_plan_need_formats",
+    "sdsj_plan_need_formats", "sdsj_png_probe_formats",
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
-FORMAT_JPEG, FORMAT_PNG = 1, 2  # SDSJ_FORMAT_*
-FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG}
+FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT = 1, 2, 4  # SDSJ_FORMAT_*
+# "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
+# valid only together with PNG, so the name carries both
+FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 def format_mask(formats) -> int:
-    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "png" (None: JPEG only, the engine's default)."""
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "png" / "png-ext" (None: JPEG only, the engine's default)."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):
@@ -144,6 +146,7 @@ def load() -> ctypes.CDLL:
         lib.sdsj_service_serve.argtypes = [ctypes.POINTER(SdsjServiceCfg)]
         lib.sdsj_engine_set_formats.argtypes = [vp, ctypes.c_int]
         lib.sdsj_png_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjPngInfo)]
+        lib.sdsj_png_probe_formats.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, ctypes.POINTER(SdsjPngInfo)]
         lib.sdsj_plan_need_formats.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjOp), ctypes.c_int,
                                                ctypes.POINTER(i64)]
         for name in EXPORTS:
@@ -160,7 +163,12 @@ def probe(jpg: bytes) -> tuple[int, SdsjInfo]:
     return st, info
 
 
-def png_probe(png: bytes) -> tuple[int, SdsjPngInfo]:
+def png_probe(png: bytes, formats=None) -> tuple[int, SdsjPngInfo]:
+    """``formats``: the SDSJ_FORMAT_* mask the sample will be decoded under (sdsj_png_probe_formats); None: the
+    base PNG subset (sdsj_png_probe)."""
     info = SdsjPngInfo()
-    st = load().sdsj_png_probe(png, len(png), ctypes.byref(info))
+    if formats is None:
+        st = load().sdsj_png_probe(png, len(png), ctypes.byref(info))
+    else:
+        st = load().sdsj_png_probe_formats(png, len(png), int(formats), ctypes.byref(info))
     return st, info

@@ -231,7 +231,7 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   if (evs) (void)hipEventRecord((*evs)[kPngEvent].get(), s);
   if (e->formats & SDSJ_FORMAT_PNG)
     SDSJ_HIP(e, launch_png(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint,
-                           evs ? (*evs)[kPngEvent + 1].get() : nullptr));
+                           evs ? (*evs)[kPngEvent + 1].get() : nullptr, e->formats));
   else if (evs)
     (void)hipEventRecord((*evs)[kPngEvent + 1].get(), s);
   mark(4);
@@ -665,8 +665,15 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
   return st;
 }
 
+// A format mask names at least one of JPEG and PNG, nothing unknown, and PNG_EXT only with PNG.
+static bool valid_formats(int mask) {
+  const int all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_PNG_EXT;
+  return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) &&
+         (!(mask & SDSJ_FORMAT_PNG_EXT) || (mask & SDSJ_FORMAT_PNG));
+}
+
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need) {
-  if (!img || !need || !valid_op(op) || !(formats & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG))) return SDSJ_EINVAL;
+  if (!img || !need || !valid_op(op) || !valid_formats(formats)) return SDSJ_EINVAL;
   int st = SDSJ_OK;
   const int64_t b = host_plan_need(img, (int64_t)n, *op, &st, nullptr, false, formats);
   *need = st == SDSJ_OK ? align_up(b, 256) : 0;
@@ -675,8 +682,7 @@ int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int 
 
 int sdsj_engine_set_formats(sdsj_engine* e, int mask) {
   if (!e) return SDSJ_EINVAL;
-  if (!(mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) || (mask & ~(SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)))
-    return fail(e, SDSJ_EINVAL, "invalid format mask");
+  if (!valid_formats(mask)) return fail(e, SDSJ_EINVAL, "invalid format mask");
   e->formats = mask;
   return SDSJ_OK;
 }

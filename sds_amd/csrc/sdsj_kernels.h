@@ -1,5 +1,5 @@
 // sdsj_kernels.h -- launchers of every stage file's gfx950 kernels (sdsj_plan.hip, sdsj_unstuff.hip,
-// sdsj_entropy.hip, sdsj_progressive.hip, sdsj_png.hip, sdsj_idct.hip, sdsj_unfused.hip, sdsj_resample.hip,
+// sdsj_entropy.hip, sdsj_progressive.hip, sdsj_png.hip, sdsj_png_ext.hip, sdsj_idct.hip, sdsj_unfused.hip, sdsj_resample.hip,
 // sdsj_resample420.hip) and host-side planning (sdsj_plan.hip); engine-internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,11 +26,17 @@ inline unsigned route_grid(uint64_t hint, int r, int64_t full) {
 hipError_t launch_parse(int n, const uint8_t* blob, int64_t blob_bytes, const int64_t* offsets, const int32_t* lengths,
                         const sdsj_op& op, int warm_bits, bool small, ImgDesc* descs, ImgTables* tables, hipStream_t s,
                         int formats = SDSJ_FORMAT_JPEG);
-// PNG samples (route kRtPng): k_png_inflate then k_png_unfilter (sdsj_png.hip); `between` (optional) is
+// PNG samples (route kRtPng): k_png_inflate then k_png_unfilter and, when `formats` has
+// SDSJ_FORMAT_PNG_EXT, k_png_unfilter_ext (sdsj_png.hip); `between` (optional) is
 // recorded between the two
 hipError_t launch_png(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                       uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
-                      uint64_t hint = kAllRoutes, hipEvent_t between = nullptr);
+                      uint64_t hint = kAllRoutes, hipEvent_t between = nullptr, int formats = SDSJ_FORMAT_PNG);
+// launch_png's kernels of the wider subset (sdsj_png_ext.hip); g: launch_png's grid
+void launch_png_inflate_ext(unsigned g, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                            uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s);
+void launch_png_unfilter_ext(unsigned g, const ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, uint8_t* scratch,
+                             const int32_t* routes, int cap, hipStream_t s);
 // base: scratch bytes a previous lane of the batch already took (device), or null
 hipError_t launch_plan(int n, ImgDesc* descs, int64_t capacity, const int64_t* base, int64_t* total, int32_t* routes,
                        int cap, hipStream_t s);

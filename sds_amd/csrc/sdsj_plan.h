@@ -252,7 +252,7 @@ SDSJ_HD int plan_sample(const Reader& rd, int64_t n, const sdsj_op& op, bool sma
   d->png = 0;
   if ((formats & SDSJ_FORMAT_PNG) && png_signature(rd, n)) {
     PngHdr ph;
-    status = png_parse(rd, n, &ph);
+    status = png_parse(rd, n, &ph, formats);
     png_fill_desc(d, ph);
     if (status == SDSJ_OK) plan_image(d, op, false, false, true);
   } else if (!(formats & SDSJ_FORMAT_JPEG)) {

@@ -4,7 +4,9 @@
 // here; the kernels add only the lane-parallel movement of bytes.
 //
 // Reference behaviour: PIL.Image.open(...).convert("RGB") (PngImagePlugin.py + ZipDecode.c + zlib).
-// Subset: non-interlaced, bit depth 8, colour types 0, 2, 3, 4, 6.  The rule is exactness: a sample is
+// Subset: non-interlaced, bit depth 8, colour types 0, 2, 3, 4, 6; with SDSJ_FORMAT_PNG_EXT in the mask
+// also Adam7 interlace, bit depths 1, 2, 4 and 16 and more ancillary chunks before the image data
+// (png_parse's `formats`, png_layout, the 64-bit png_recon, png_rgb_ext).  The rule is exactness: a sample is
 // reported SDSJ_OK only where PIL decodes the same bytes to the same pixels without raising; everything
 // this code is not sure about is SDSJ_UNSUPPORTED (a valid file outside the subset) or SDSJ_CORRUPT
 // (anything malformed), and the transforms rerun both on PIL, which then decides.
@@ -25,7 +27,7 @@ namespace sdsj {
 
 struct PngHdr {
   int32_t width, height, bit_depth, ctype, interlace;
-  int32_t bpp;       // bytes per pixel of the scanlines (bit depth 8)
+  int32_t bpp;       // the filter unit: bytes per pixel of the scanlines, 1 for depths below 8 (png_unit)
   int32_t plte_n;    // PLTE entries (0: none)
   int32_t zero;
   int64_t plte_pos;  // first PLTE data byte
@@ -35,6 +37,85 @@ struct PngHdr {
 constexpr int64_t kPngMaxPixels = 89478485;      // PIL Image.MAX_IMAGE_PIXELS: above it Image.open warns or raises
 constexpr int64_t kPngMaxHeader = 1 << 20;       // bytes before the first IDAT this path walks
 constexpr int64_t kPngMaxRaw = (int64_t)1 << 30;  // inflated scanline bytes of one image
+
+// ------------------------------------------------------------------------------------------
+// Scanline layout (PNG specification 7.2, 8.2, 9.2).  The filter unit is the whole bytes of a pixel,
+// 1 for depths below 8.  A non-interlaced image is one pass; an Adam7 image has up to seven, each a
+// complete filtered image of its own (pass width x pass height, its upper row starting as zeros), and
+// a pass without columns or rows contributes no bytes at all, not even filter bytes.
+// ------------------------------------------------------------------------------------------
+SDSJ_HD inline int png_channels(int ctype) { return ctype == 2 ? 3 : ctype == 4 ? 2 : ctype == 6 ? 4 : 1; }
+SDSJ_HD inline int png_unit(int ctype, int depth) {
+  const int u = png_channels(ctype) * depth / 8;
+  return u < 1 ? 1 : u;
+}
+
+struct PngPass {
+  int32_t xs, ys, dx, dy;  // image x = xs + px * dx, y = ys + py * dy
+  int32_t w, h;            // pass size in pixels
+  int64_t rowbytes;        // ceil(w * bits per pixel / 8), without the filter byte
+  int64_t off;             // first byte (row 0's filter byte) of the pass in the inflated buffer
+};
+
+// Geometry of pass `slot` (0: the whole image of a non-interlaced file; 0..6: the Adam7 passes) and the
+// bytes of the passes before it; false: the pass is empty.  No table in memory: the kernels call this
+// with a wave-uniform slot.
+SDSJ_HD inline bool png_pass_at(int w, int h, int ctype, int depth, int interlace, int slot, PngPass* ps) {
+  const int64_t bits = (int64_t)png_channels(ctype) * depth;
+  const int np = interlace ? 7 : 1;
+  int64_t off = 0;
+  for (int p = 0; p < np; p++) {
+    // (x start, y start, x step, y step) of the Adam7 passes: 0,0,8,8  4,0,8,8  0,4,4,8  2,0,4,4  0,2,2,4
+    // 1,0,2,2  0,1,1,2.  The steps as shifts; an odd pass starts half an x step in, an even pass
+    // after the first half a y step down.
+    const int lx = interlace ? 3 - (p >> 1) : 0, ly = interlace ? 3 - (p >> 1) + (p > 0 && !(p & 1)) : 0;
+    const int xs = (p & 1) ? (1 << lx) >> 1 : 0;
+    const int ys = p >= 2 && !(p & 1) ? (1 << ly) >> 1 : 0;
+    const int pw = w > xs ? (w - xs + (1 << lx) - 1) >> lx : 0;
+    const int ph = h > ys ? (h - ys + (1 << ly) - 1) >> ly : 0;
+    const int64_t rb = ((int64_t)pw * bits + 7) >> 3;
+    const bool some = pw > 0 && ph > 0;
+    if (p == slot) {
+      ps->xs = xs;
+      ps->ys = ys;
+      ps->dx = 1 << lx;
+      ps->dy = 1 << ly;
+      ps->w = pw;
+      ps->h = ph;
+      ps->rowbytes = rb;
+      ps->off = off;
+      return some;
+    }
+    if (some) off += (int64_t)ph * (1 + rb);
+  }
+  ps->xs = ps->ys = ps->w = ps->h = 0;
+  ps->dx = ps->dy = 1;
+  ps->rowbytes = 0;
+  ps->off = off;  // slot == number of passes: the exact inflated size
+  return false;
+}
+
+// The exact inflated size: the sum of the non-empty passes.
+SDSJ_HD inline int64_t png_layout_bytes(int w, int h, int ctype, int depth, int interlace) {
+  PngPass ps;
+  png_pass_at(w, h, ctype, depth, interlace, interlace ? 7 : 1, &ps);
+  return ps.off;
+}
+
+// The whole layout for host code: the filter unit, the non-empty passes in stream order, the total.
+struct PngLayout {
+  int32_t unit, npass;
+  int64_t total;
+  PngPass pass[7];
+};
+
+SDSJ_HD inline void png_layout(int w, int h, int ctype, int depth, int interlace, PngLayout* L) {
+  L->unit = png_unit(ctype, depth);
+  L->npass = 0;
+  for (int p = 0; p < (interlace ? 7 : 1); p++)
+    if (png_pass_at(w, h, ctype, depth, interlace, p, &L->pass[L->npass])) L->npass++;
+  L->total = png_layout_bytes(w, h, ctype, depth, interlace);
+}
 
 SDSJ_HD inline uint32_t png_crc_byte(uint32_t c, int b) {  // CRC-32 (reflected 0xEDB88320), one byte, no table
   c ^= (uint32_t)b;
@@ -62,8 +143,18 @@ SDSJ_HD inline bool png_signature(const Reader& rd, int64_t n) {
 // error there; a chunk whose handler could raise or that this path has not been checked against
 // (iCCP, zTXt, iTXt, acTL, ... and unknown ones) hands the sample over instead of guessing.
 // h's IHDR fields are filled as soon as IHDR has been read, whatever the status.
+//
+// formats with SDSJ_FORMAT_PNG_EXT: Adam7 files and every legal (colour type, depth) pair are accepted,
+// and so is an ancillary chunk (bit 5 of the first type byte, four ASCII letters -- ChunkStream.read
+// raises on a type that is_cid does not match, PngImagePlugin.py:63, :181) that PngStream has no
+// chunk_XXXX method for: PngImageFile._open then reads it and checks its CRC like every other
+// (:786-792).  The methods of Pillow 12.2.0 are chunk_iCCP :424, IHDR :452, IDAT :473, IEND :486, PLTE
+// :490, tRNS :498, gAMA :521, cHRM :528, sRGB :538, pHYs :555, tEXt :573, zTXt :593, iTXt :628, eXIf
+// :671, acTL :678, fcTL :699, fdAT :729.  eXIf's only stores the bytes (:671-675) and is accepted too;
+// iCCP, zTXt and iTXt inflate data and can raise, the APNG chunks change what is decoded: PIL decides.
 template <class Reader>
-SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h) {
+SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h, int formats = SDSJ_FORMAT_PNG) {
+  const bool ext = (formats & SDSJ_FORMAT_PNG_EXT) != 0;
   h->width = h->height = h->bit_depth = h->ctype = h->interlace = h->bpp = h->plte_n = h->zero = 0;
   h->plte_pos = h->idat_pos = 0;
   if (!png_signature(rd, n)) return SDSJ_UNSUPPORTED;
@@ -97,7 +188,7 @@ SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h) {
       const bool pow2 = bd == 1 || bd == 2 || bd == 4 || bd == 8 || bd == 16;
       const bool legal = pow2 && (ct == 0 || (ct == 3 && bd <= 8) || ((ct == 2 || ct == 4 || ct == 6) && bd >= 8));
       if (!legal) return SDSJ_CORRUPT;
-      h->bpp = ct == 0 || ct == 3 ? 1 : ct == 4 ? 2 : ct == 2 ? 3 : 4;
+      h->bpp = png_unit(ct, bd);
     } else if (tag == png_tag('P', 'L', 'T', 'E')) {
       if (h->plte_n || len == 0 || len > 768 || len % 3) return SDSJ_UNSUPPORTED;
       h->plte_n = (int32_t)(len / 3);
@@ -115,17 +206,31 @@ SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h) {
     } else if (tag == png_tag('t', 'E', 'X', 't')) {
       if (len > 65536) return SDSJ_UNSUPPORTED;
     } else {
-      return SDSJ_UNSUPPORTED;  // acTL (APNG), iCCP, zTXt, iTXt, eXIf, unknown chunks: PIL decides
+      // acTL (APNG), iCCP, zTXt, iTXt, unknown critical chunks: PIL decides; so it does for eXIf and the
+      // ancillary chunks it has no handler for unless the mask has SDSJ_FORMAT_PNG_EXT
+      bool letters = true;
+      for (int k = 0; k < 4; k++) {
+        const int c = (int)((tag >> (8 * k)) & 255u) | 32;
+        letters = letters && c >= 'a' && c <= 'z';
+      }
+      const bool handled = tag == png_tag('i', 'C', 'C', 'P') || tag == png_tag('z', 'T', 'X', 't') ||
+                           tag == png_tag('i', 'T', 'X', 't') || tag == png_tag('a', 'c', 'T', 'L') ||
+                           tag == png_tag('f', 'c', 'T', 'L') || tag == png_tag('f', 'd', 'A', 'T');
+      if (!ext || !letters || !((tag >> 29) & 1u) || handled) return SDSJ_UNSUPPORTED;
     }
     p += 12 + (int64_t)len;
   }
   if (first) return SDSJ_CORRUPT;
-  if (h->interlace || h->bit_depth != 8) return SDSJ_UNSUPPORTED;
+  if (!ext && (h->interlace || h->bit_depth != 8)) return SDSJ_UNSUPPORTED;
   if ((int64_t)h->width * h->height > kPngMaxPixels || h->width > 65535 || h->height > 65535) return SDSJ_UNSUPPORTED;
-  if ((int64_t)h->height * (1 + (int64_t)h->width * h->bpp) > kPngMaxRaw) return SDSJ_UNSUPPORTED;
+  const bool plain = h->bit_depth == 8 && !h->interlace;  // one pass of whole-byte pixels: no walk over the passes
+  const int64_t raw = plain ? (int64_t)h->height * (1 + (int64_t)h->width * h->bpp)
+                            : png_layout_bytes(h->width, h->height, h->ctype, h->bit_depth, h->interlace);
+  if (raw > kPngMaxRaw) return SDSJ_UNSUPPORTED;
   return SDSJ_OK;
 }
 
+// The inflated size of a non-interlaced image of whole-byte pixels (png_layout_bytes in general).
 SDSJ_HD inline int64_t png_raw_bytes(int w, int h, int bpp) { return (int64_t)h * (1 + (int64_t)w * bpp); }
 
 // ------------------------------------------------------------------------------------------
@@ -512,6 +617,16 @@ SDSJ_HD inline uint32_t png_recon(int ft, uint32_t raw, uint32_t a, uint32_t b, 
   return r;
 }
 
+// The same over a filter unit of up to 8 bytes (16-bit samples: 2, 4, 6 or 8 bytes a pixel), byte k of
+// the unit at bits 8k.
+SDSJ_HD inline uint64_t png_recon(int ft, uint64_t raw, uint64_t a, uint64_t b, uint64_t c, int unit) {
+  const uint32_t lo = png_recon(ft, (uint32_t)raw, (uint32_t)a, (uint32_t)b, (uint32_t)c, unit < 4 ? unit : 4);
+  const uint32_t hi = unit > 4 ? png_recon(ft, (uint32_t)(raw >> 32), (uint32_t)(a >> 32), (uint32_t)(b >> 32),
+                                           (uint32_t)(c >> 32), unit - 4)
+                               : 0u;
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
 // The reconstructed pixel as convert("RGB") gives it: gray replicated, alpha dropped (no
 // premultiplication), palette entries looked up -- (0, 0, 0) at or beyond the PLTE length or without
 // a PLTE.  `pal(i)` returns palette byte i (3 per entry).  Returns r | g << 8 | b << 16.
@@ -528,6 +643,28 @@ SDSJ_HD inline uint32_t png_rgb(int ctype, uint32_t px, int plte_n, const Pal& p
     default:
       return px & 0xFFFFFFu;
   }
+}
+
+// Pixel k of a reconstructed filter unit at any depth, as convert("RGB") gives it.  Depths 1, 2, 4: the
+// unit is one byte of 8 / 4 / 2 samples, most significant bits first (the caller drops those beyond
+// the row's width); gray samples scale by 255 / 85 / 17, palette indices are looked up as png_rgb does.
+// Depth 16, samples big-endian: gray alone opens as I;16 and convert("RGB") clips the value to 255;
+// gray + alpha, RGB and RGBA keep the high byte of each colour sample.  k is 0 from depth 8 on.
+template <class Pal>
+SDSJ_HD inline uint32_t png_rgb_ext(int ctype, int depth, uint64_t unit, int k, int plte_n, const Pal& pal) {
+  if (depth == 8) return png_rgb(ctype, (uint32_t)unit, plte_n, pal);
+  if (depth < 8) {
+    const uint32_t mask = (1u << depth) - 1u;
+    const uint32_t v = ((uint32_t)unit >> (8 - depth * (k + 1))) & mask;
+    return png_rgb(ctype, ctype == 3 ? v : v * (255u / mask), plte_n, pal);
+  }
+  const uint32_t b0 = (uint32_t)unit & 255u, b1 = (uint32_t)(unit >> 8) & 255u;
+  if (ctype == 0) {
+    const uint32_t v = b0 ? 255u : b1;  // min((b0 << 8) | b1, 255)
+    return v | (v << 8) | (v << 16);
+  }
+  if (ctype == 4) return b0 | (b0 << 8) | (b0 << 16);
+  return b0 | ((uint32_t)(unit >> 16) & 255u) << 8 | ((uint32_t)(unit >> 32) & 255u) << 16;
 }
 
 // The descriptor of a parsed PNG: no components, blocks or entropy data, so every JPEG kernel that
@@ -551,7 +688,10 @@ SDSJ_HD inline void png_fill_desc(ImgDesc* d, const PngHdr& h) {
   d->png_plte_n = h.plte_n;
   d->png_plte_pos = h.plte_pos;
   d->png_idat_pos = h.idat_pos;
-  d->png_raw = png_raw_bytes(h.width, h.height, h.bpp);
+  // (a header png_parse refused may hold any sizes: nothing reads png_raw then)
+  if (h.bit_depth == 8 && !h.interlace) d->png_raw = png_raw_bytes(h.width, h.height, h.bpp);
+  else d->png_raw = h.width <= 65535 && h.height <= 65535 ? png_layout_bytes(h.width, h.height, h.ctype, h.bit_depth, h.interlace) : 0;
+  d->etab_pad = (h.bit_depth & 255) | ((h.interlace & 255) << 8);  // (padding the struct already had: its size is pinned)
   d->off_png = 0;
 }
 

@@ -199,6 +199,10 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
     is meant for batched use (GpuDecodeBatch): a single-image call has a longer latency than PIL's decode.
+    ``"png-ext"`` (it includes ``"png"``) widens the subset to Adam7-interlaced files, bit depths 1, 2, 4 and
+    16 and files with tIME / bKGD / sBIT / eXIf or private ancillary chunks; APNG and files with iCCP, zTXt
+    or iTXt chunks still rerun on PIL.  Under ``"png-ext"`` the inflate kernel also walks the pass layout, which
+    measured 2 % slower on plain 8-bit files (6.18k against 6.32k images/s, ``profiles/png_ext_bench.jsonl``): a shard of those alone is better served by ``"png"``.
     In a served worker process (the decode service) PNG samples keep the PIL route whatever this says: the
     service's wire protocol carries no format mask.
     """
@@ -244,8 +248,9 @@ class GpuDecodeResizeImageTransform(BaseTransform):
         # again, after PIL's decode, as the reference does) leaves the RNGs one draw ahead, not two
         rng = _RngSnapshot(kw.get("random_resize") is not None, self.hflip_prob > 0.0)
         if need_size:
-            if eng is not None and "png" in self.gpu_formats and data[:8] == _lib.PNG_SIGNATURE:
-                st, info = _lib.png_probe(data)
+            mask = _lib.format_mask(self.gpu_formats)
+            if eng is not None and mask & _lib.FORMAT_PNG and data[:8] == _lib.PNG_SIGNATURE:
+                st, info = _lib.png_probe(data, mask)  # (under the mask: a "png-ext" file is sized natively)
             else:
                 st, info = _lib.probe(data)
             if st != _lib.OK or info.width <= 0 or info.height <= 0:  # not a JPEG this path decodes
@@ -538,7 +543,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"png"`` to opt in; see GpuDecodeResizeImageTransform).
+    formats decoded natively (add ``"png"`` or ``"png-ext"`` to opt in; see GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
     the pipeline gets device tensors (it decodes in-process), while its forked DataLoader workers get

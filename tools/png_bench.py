@@ -8,7 +8,12 @@ a pool of 64 synthetic 640x480 RGB PNGs (synth_rgb, Pillow's default compression
   latency    one-image calls through the per-sample transform, native and default route (ms per image)
 
 The native line carries bench.cpu_baseline over the pool written to files, on 1 and 16 cores, and the
-engine's stage times (png_inflate / png_unfilter among them).  `python tools/png_bench.py N [route ...]`."""
+engine's stage times (png_inflate / png_unfilter among them).  `python tools/png_bench.py N [route ...]`.
+
+`--ext` measures the wider subset instead (formats=("jpeg", "png-ext"), k_png_unfilter_ext): the same 64
+images as Adam7-interlaced RGB (written by tests/png_ext_synth.py, Pillow writes no interlaced files) and as
+4-bit palette files (Pillow's quantize to 16 colours, bits=4), after the base pool itself under the full mask;
+every line then carries a "case"."""
 import io
 import json
 import os
@@ -19,6 +24,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 BOTH = ("jpeg", "png")
+EXT = ("jpeg", "png-ext")
 
 
 def make_pool():
@@ -34,7 +40,25 @@ def make_pool():
     return pool
 
 
-def native(pool, n):
+def make_ext_pools():
+    import numpy as np
+    from PIL import Image
+
+    from tests import png_ext_synth as E
+    from tests import png_synth as S
+    from tests.golden.synth import synth_rgb
+    adam7, pal4 = [], []
+    for i in range(64):
+        rgb = synth_rgb(np.random.default_rng(1234 + i), 640, 480)
+        raw = E.raw_stream(rgb.astype(np.uint16), 2, 8, 1, "all4")
+        adam7.append(S.write_png(640, 480, 2, S.zstream(raw, 6), interlace=1))
+        b = io.BytesIO()
+        Image.fromarray(rgb).quantize(16).save(b, "PNG", bits=4)
+        pal4.append(b.getvalue())
+    return [("adam7 RGB", adam7), ("4-bit palette", pal4)]
+
+
+def native(pool, n, formats=BOTH, case=None):
     import numpy as np
     import torch
 
@@ -45,19 +69,19 @@ def native(pool, n):
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     blob = torch.from_numpy(np.frombuffer(b"".join(pngs), np.uint8).copy()).cuda()
     d_offs, d_lens = torch.from_numpy(offs).cuda(), torch.tensor(lens, dtype=torch.int32).cuda()
-    need = JpegEngine.scratch_need(pool, (256, 256), formats=BOTH) * ((n + len(pool) - 1) // len(pool))
+    need = JpegEngine.scratch_need(pool, (256, 256), formats=formats) * ((n + len(pool) - 1) // len(pool))
     eng = JpegEngine(max_batch=n, scratch_bytes=need + (64 << 20))
-    out, st = eng.decode_resize_device(blob, d_offs, d_lens, (256, 256), formats=BOTH)
+    out, st = eng.decode_resize_device(blob, d_offs, d_lens, (256, 256), formats=formats)
     torch.cuda.synchronize()
     assert (st == 0).all(), st[st != 0][:8]
     assert eng.counters()["png"] == n
     t0 = time.perf_counter()
     for _ in range(3):
-        eng.decode_resize_device(blob, d_offs, d_lens, (256, 256), out=out, status=st, formats=BOTH)
+        eng.decode_resize_device(blob, d_offs, d_lens, (256, 256), out=out, status=st, formats=formats)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 3
     eng.set_timing(True)
-    eng.decode_resize_device(blob, d_offs, d_lens, (256, 256), out=out, status=st, formats=BOTH)
+    eng.decode_resize_device(blob, d_offs, d_lens, (256, 256), out=out, status=st, formats=formats)
     stages = {k: round(v, 3) for k, v in eng.stage_times().items() if v > 0.0005}
     eng.set_timing(False)
     folder = tempfile.mkdtemp()
@@ -69,7 +93,8 @@ def native(pool, n):
     procs = min(16, bench.host_cores())
     cpu1 = bench.cpu_baseline(paths, 1, 2.0)
     cpup = bench.cpu_baseline(paths, procs, 4.0)
-    print(json.dumps({"route": "native", "metric": "images/s PNG 640x480 RGB decode+resize@256 (device-resident)",
+    print(json.dumps({"route": "native", **({"case": case} if case else {}),
+                      "metric": f"images/s PNG 640x480 {case or 'RGB'} decode+resize@256 (device-resident)",
                       "value": round(n / dt, 1), "batch": n, "mean_png_bytes": round(float(np.mean(lens)), 1),
                       "stage_ms": stages,
                       "cpu_baseline": {"value": round(cpup, 1), "cores": procs, "single_core_value": round(cpu1, 1),
@@ -77,7 +102,7 @@ def native(pool, n):
                                        "CHW tensor over the 64 pool PNGs read from files"}}), flush=True)
 
 
-def fallback(pool, n):
+def fallback(pool, n, formats=BOTH, case=None):
     import torch
 
     from sds_amd.batched import GpuDecodeBatch
@@ -93,12 +118,13 @@ def fallback(pool, n):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert get_engine("cuda").counters()["fallback"] - c0["fallback"] == n
-    print(json.dumps({"route": "fallback", "metric": "images/s PNG 640x480 RGB, GpuDecodeBatch default gpu_formats "
+    print(json.dumps({"route": "fallback", **({"case": case} if case else {}),
+                      "metric": f"images/s PNG 640x480 {case or 'RGB'}, GpuDecodeBatch default gpu_formats "
                       "(PIL decode per sample in the calling process, resize on the GPU)",
                       "value": round(n / dt, 1), "batch": n}), flush=True)
 
 
-def latency(pool, n):
+def latency(pool, n, formats=BOTH, case=None):
     import torch
 
     from sds_amd.presets import create_standard_image_pipeline
@@ -109,7 +135,7 @@ def latency(pool, n):
         with open(paths[-1], "wb") as f:
             f.write(j)
     res = {}
-    for name, fm in (("native_ms", BOTH), ("default_route_ms", ("jpeg",))):
+    for name, fm in (("native_ms", formats), ("default_route_ms", ("jpeg",))):
         ts = create_standard_image_pipeline("png", (256, 256), device="cuda", service=None, gpu_formats=fm)
         for rep in range(2):  # (the first pass warms up)
             torch.cuda.synchronize()
@@ -120,16 +146,21 @@ def latency(pool, n):
                     s = t(s)
             torch.cuda.synchronize()
             res[name] = round((time.perf_counter() - t0) / len(paths) * 1e3, 3)
-    print(json.dumps({"route": "latency", "metric": "ms per one-image call, per-sample transform, PNG 640x480 RGB -> 256x256",
+    print(json.dumps({"route": "latency", **({"case": case} if case else {}),
+                      "metric": f"ms per one-image call, per-sample transform, PNG 640x480 {case or 'RGB'} -> 256x256",
                       **res}), flush=True)
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-    routes = sys.argv[2:] or ["native", "fallback", "latency"]
-    pool = make_pool()
-    for r in routes:
-        {"native": native, "fallback": fallback, "latency": latency}[r](pool, n)
+    args = [a for a in sys.argv[1:] if a != "--ext"]
+    ext = "--ext" in sys.argv[1:]
+    n = int(args[0]) if args else 4096
+    routes = args[1:] or ["native", "fallback", "latency"]
+    # (--ext: the base pool too, so that what the full mask costs plain 8-bit files is on record)
+    pools = [("RGB under png-ext", make_pool())] + make_ext_pools() if ext else [(None, make_pool())]
+    for case, pool in pools:
+        for r in routes:
+            {"native": native, "fallback": fallback, "latency": latency}[r](pool, n, EXT if ext else BOTH, case)
 
 
 if __name__ == "__main__":
