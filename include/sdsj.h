@@ -107,10 +107,19 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * palette 1 / 2 / 4, gray 16 clipped to 255 (PIL opens it as I;16), the high byte of gray + alpha, RGB
  * and RGBA 16 -- and, before the image data, eXIf and every ancillary chunk PIL has no handler for
  * (tIME, bKGD, sBIT, private ones; CRC checked).  APNG, iCCP, zTXt and iTXt stay SDSJ_UNSUPPORTED.
- * Without the bit nothing changes: those files report SDSJ_UNSUPPORTED. */
+ * Without the bit nothing changes: those files report SDSJ_UNSUPPORTED.
+ *
+ * SDSJ_FORMAT_PNG_META (valid only together with SDSJ_FORMAT_PNG, SDSJ_EINVAL otherwise; it may be combined
+ * with SDSJ_FORMAT_PNG_EXT) accepts files as converters and editors write them: iCCP, zTXt and iTXt chunks
+ * -- none changes a pixel of convert("RGB") -- and chunks after the image data (tEXt, gAMA, cHRM, sRGB,
+ * pHYs, iCCP, zTXt, iTXt; with SDSJ_FORMAT_PNG_EXT also eXIf and the ancillary chunks PIL has no handler
+ * for).  A compressed chunk is accepted only where its zlib stream is well formed and inflates to fewer than
+ * 1,048,576 bytes (PIL raises above that), the text chunks of a file only up to 67,108,864 bytes in all
+ * (PIL's limit); everything else, and APNG, stays SDSJ_UNSUPPORTED.  Without the bit nothing changes. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
 #define SDSJ_FORMAT_PNG_EXT 4
+#define SDSJ_FORMAT_PNG_META 16
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -123,7 +132,9 @@ typedef struct sdsj_png_info {
 int sdsj_png_probe(const uint8_t* png, size_t n, sdsj_png_info* out);
 
 /* The same for an engine whose format mask is `formats` (it must have SDSJ_FORMAT_PNG): with
- * SDSJ_FORMAT_PNG_EXT the wider subset is `supported`; without it the result is sdsj_png_probe's. */
+ * SDSJ_FORMAT_PNG_EXT the wider subset is `supported`; without it the result is sdsj_png_probe's.  With
+ * SDSJ_FORMAT_PNG_META the status is the one the sample has before its image data is inflated: the
+ * compressed chunks and the chunks after the image data are judged too (the whole file is walked). */
 int sdsj_png_probe_formats(const uint8_t* png, size_t n, int formats, sdsj_png_info* out);
 
 /* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
@@ -207,7 +218,7 @@ int sdsj_resize_frames_device(sdsj_engine* eng, int n, const uint8_t* d_frames, 
 #define SDSJ_CTR_BYTES_OUT 7   /* output tensor bytes written (failed samples included: zeros) */
 #define SDSJ_CTR_FRAMES 8      /* raw frames resized (sdsj_resize_frames_device) */
 #define SDSJ_CTR_PROGRESSIVE 9 /* progressive JPEGs decoded */
-#define SDSJ_CTR_PNG 10        /* PNG samples decoded natively (SDSJ_FORMAT_PNG, SDSJ_FORMAT_PNG_EXT) */
+#define SDSJ_CTR_PNG 10        /* PNG samples decoded natively (SDSJ_FORMAT_PNG and its _EXT / _META bits) */
 #define SDSJ_NUM_COUNTERS 11
 int sdsj_engine_counters(sdsj_engine* eng, uint64_t* out, int cap, int reset);
 const char* sdsj_counter_name(int k);

@@ -37,15 +37,18 @@ EXPORTS = [
     "sdsj_plan_need_formats", "sdsj_png_probe_formats",
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
-FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT = 1, 2, 4  # SDSJ_FORMAT_*
+FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META = 1, 2, 4, 16  # SDSJ_FORMAT_*
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
 # valid only together with PNG, so the name carries both
-FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT}
+# "png-meta": PNG files as converters and editors write them (iCCP, zTXt, iTXt, chunks after the image data);
+# likewise valid only together with PNG, and combinable with "png-ext"
+FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT,
+           "png-meta": FORMAT_PNG | FORMAT_PNG_META}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 def format_mask(formats) -> int:
-    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "png" / "png-ext" (None: JPEG only, the engine's default)."""
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "png" / "png-ext" / "png-meta" (None: JPEG only, the engine's default)."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):

@@ -228,7 +228,8 @@ class GpuDecodeBatch:
     ``return_image_as_single_frame_video`` mirrors presets.py:737-742 on the batch: ``video`` =
     ``[B, 1, 3, H, W]``, ``image`` removed, ``framerate`` = 960.0 per sample (float64, as
     default_collate stacks Python floats).
-    ``gpu_formats``: the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"png"`` / ``"png-ext"``
+    ``gpu_formats``: the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"png"`` / ``"png-ext"`` /
+    ``"png-meta"``
     (default JPEG only; see presets.GpuDecodeResizeImageTransform).  With ``"png"`` a PNG shard no longer
     decodes one sample at a time on a host core; PNG on the GPU is meant for this batched use.
     """

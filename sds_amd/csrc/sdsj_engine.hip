@@ -214,6 +214,8 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   mark(0);
   SDSJ_HIP(e, launch_parse(n, d_blob, blob_bytes, d_offsets, d_lengths, op, e->warm_bits, small, ln.descs, ln.tables, s,
                            e->formats));
+  if ((e->formats & SDSJ_FORMAT_PNG) && (e->formats & SDSJ_FORMAT_PNG_META))  // (counts under "parse")
+    SDSJ_HIP(e, launch_png_meta(n, ln.descs, d_blob, d_offsets, d_lengths, s, e->formats));
   mark(1);
   const int cap = e->max_batch;
   SDSJ_HIP(e, launch_plan(n, ln.descs, e->capacity(), ln.base, ln.total, ln.routes, cap, s));
@@ -665,11 +667,11 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
   return st;
 }
 
-// A format mask names at least one of JPEG and PNG, nothing unknown, and PNG_EXT only with PNG.
+// A format mask names at least one of JPEG and PNG, nothing unknown, and PNG_EXT and PNG_META (alone or
+// together) only with PNG.
 static bool valid_formats(int mask) {
-  const int all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_PNG_EXT;
-  return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) &&
-         (!(mask & SDSJ_FORMAT_PNG_EXT) || (mask & SDSJ_FORMAT_PNG));
+  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | sub;
+  return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG));
 }
 
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need) {

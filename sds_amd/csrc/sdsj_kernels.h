@@ -37,6 +37,16 @@ void launch_png_inflate_ext(unsigned g, ImgDesc* descs, const uint8_t* blob, con
                             uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s);
 void launch_png_unfilter_ext(unsigned g, const ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, uint8_t* scratch,
                              const int32_t* routes, int cap, hipStream_t s);
+// SDSJ_FORMAT_PNG_META (sdsj_png_meta.hip).  launch_png_meta: k_png_meta between k_parse and k_plan -- the
+// compressed chunks and the chunks after the image data of every PNG sample k_parse accepted, refused ones
+// turned SDSJ_UNSUPPORTED before anything is planned for them.  launch_png_inflate_meta: launch_png's
+// inflate kernel under that mask (with or without SDSJ_FORMAT_PNG_EXT), which leaves the tail to k_png_meta.
+hipError_t launch_png_meta(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                           hipStream_t s, int formats);
+void launch_png_inflate_meta(unsigned g, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                             uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s);
+// The host's side of k_png_meta (host planning, the probe): png_meta_check on one sample png_parse accepted.
+int host_png_meta(const uint8_t* png, int64_t n, int64_t idat_pos, int formats);
 // base: scratch bytes a previous lane of the batch already took (device), or null
 hipError_t launch_plan(int n, ImgDesc* descs, int64_t capacity, const int64_t* base, int64_t* total, int32_t* routes,
                        int cap, hipStream_t s);

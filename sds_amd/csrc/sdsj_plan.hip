@@ -340,7 +340,9 @@ int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* st
   ImgDesc d;
   static thread_local ImgTables t;
   MemReader rd{jpg};
-  const int st = plan_sample(rd, n, op, small, formats, &d, &t, CopySink<MemReader>{rd});
+  int st = plan_sample(rd, n, op, small, formats, &d, &t, CopySink<MemReader>{rd});
+  // (the device runs this check in a kernel of its own between k_parse and k_plan: launch_png_meta)
+  if (st == SDSJ_OK && d.png && (formats & SDSJ_FORMAT_PNG_META)) st = host_png_meta(jpg, n, d.png_idat_pos, formats);
   *status = st;
   if (routes) {
     *routes = kAllRoutes;

@@ -6,7 +6,8 @@
 // Reference behaviour: PIL.Image.open(...).convert("RGB") (PngImagePlugin.py + ZipDecode.c + zlib).
 // Subset: non-interlaced, bit depth 8, colour types 0, 2, 3, 4, 6; with SDSJ_FORMAT_PNG_EXT in the mask
 // also Adam7 interlace, bit depths 1, 2, 4 and 16 and more ancillary chunks before the image data
-// (png_parse's `formats`, png_layout, the 64-bit png_recon, png_rgb_ext).  The rule is exactness: a sample is
+// (png_parse's `formats`, png_layout, the 64-bit png_recon, png_rgb_ext); with SDSJ_FORMAT_PNG_META also
+// iCCP, zTXt and iTXt chunks and chunks after the image data (png_meta_check).  The rule is exactness: a sample is
 // reported SDSJ_OK only where PIL decodes the same bytes to the same pixels without raising; everything
 // this code is not sure about is SDSJ_UNSUPPORTED (a valid file outside the subset) or SDSJ_CORRUPT
 // (anything malformed), and the transforms rerun both on PIL, which then decides.
@@ -138,10 +139,97 @@ SDSJ_HD inline bool png_signature(const Reader& rd, int64_t n) {
          rd(6) == 0x1A && rd(7) == 0x0A;
 }
 
+// ------------------------------------------------------------------------------------------
+// iCCP, zTXt and iTXt (SDSJ_FORMAT_PNG_META).  Their handlers in PngImagePlugin.py inflate a zlib stream
+// with _safe_zlib_decompress (:145), which raises ValueError only when kPngMaxTextChunk bytes have been
+// produced and input is left, and swallow zlib.error; the text chunks add their character counts to a
+// budget (check_text_memory :403) that raises above kPngMaxTextMemory.
+// ------------------------------------------------------------------------------------------
+constexpr int64_t kPngMaxTextChunk = 1 << 20;    // PngImagePlugin.MAX_TEXT_CHUNK
+constexpr int64_t kPngMaxTextMemory = 64 << 20;  // PngImagePlugin.MAX_TEXT_MEMORY
+
+template <class Reader>
+SDSJ_HDI int64_t png_find_nul(const Reader& rd, int64_t p, int64_t e) {  // the first 0 byte of [p, e), or e
+  while (p < e && rd(p) != 0) p++;
+  return p;
+}
+
+// What the handler of a compressed-metadata chunk with payload [p, e) does.  0: it raises (or this path
+// does not know): PIL decides.  1: it accepts without inflating; *text = the bytes that join the text
+// budget.  2: it inflates [*zs, e): accepted iff that stream passes the size rule (png_inflate_count), its
+// inflated size then joins the budget when *text is 1.  Every byte read lies in [p, e).
+//   chunk_iCCP :424  i = s.find(b"\0"), method = s[i + 1] (IndexError when missing, SyntaxError when not
+//                    0; without a NUL i = -1 and the method is s[0], which is then not 0), stream s[i+2:]
+//   chunk_zTXt :593  split at the first NUL; no NUL or nothing after it: method 0, empty stream, accepted;
+//                    otherwise the method must be 0; the text counts when the key is not empty
+//   chunk_iTXt :628  early returns (no NUL, fewer than two bytes after it, fewer than two further NULs, a
+//                    compressed text with a method other than 0) add nothing; a text's byte length bounds
+//                    its character count
+template <class Reader>
+SDSJ_HDI int png_meta_stream(const Reader& rd, uint32_t tag, int64_t p, int64_t e, int64_t* zs, int64_t* text) {
+  *zs = e;
+  *text = 0;
+  const int64_t i = png_find_nul(rd, p, e);
+  if (tag == png_tag('i', 'C', 'C', 'P')) {
+    if (i + 1 >= e || rd(i + 1) != 0) return 0;
+    *zs = i + 2;
+    return 2;
+  }
+  if (tag == png_tag('z', 'T', 'X', 't')) {
+    if (i + 1 >= e) return 1;
+    if (rd(i + 1) != 0) return 0;
+    *zs = i + 2;
+    *text = i > p;
+    return 2;
+  }
+  if (tag != png_tag('i', 'T', 'X', 't')) return 0;
+  if (i >= e || e - (i + 1) < 2) return 1;
+  const int cf = rd(i + 1), cm = rd(i + 2);
+  const int64_t j = png_find_nul(rd, i + 3, e);
+  if (j >= e) return 1;
+  const int64_t k = png_find_nul(rd, j + 1, e);
+  if (k >= e) return 1;
+  if (cf == 0) {
+    *text = e - (k + 1);
+    return 1;
+  }
+  if (cm != 0) return 1;
+  *zs = k + 1;
+  *text = 1;
+  return 2;
+}
+
+// The rule for one chunk that is neither IHDR, PLTE, tRNS, IDAT nor IEND, before the image data and --
+// with SDSJ_FORMAT_PNG_META -- after it: its type and length, and for iCCP / zTXt the method byte.  (The
+// zlib streams and the text budget are png_meta_chunk's.)  [p, p + len) is the payload, inside the input.
+template <class Reader>
+SDSJ_HDI bool png_chunk_ok(const Reader& rd, uint32_t tag, int64_t p, uint32_t len, int formats) {
+  if (tag == png_tag('g', 'A', 'M', 'A')) return len == 4;
+  if (tag == png_tag('c', 'H', 'R', 'M')) return len == 32;
+  if (tag == png_tag('s', 'R', 'G', 'B')) return len == 1;
+  if (tag == png_tag('p', 'H', 'Y', 's')) return len == 9;
+  if (tag == png_tag('t', 'E', 'X', 't')) return len <= 65536;
+  if (tag == png_tag('i', 'C', 'C', 'P') || tag == png_tag('z', 'T', 'X', 't') || tag == png_tag('i', 'T', 'X', 't')) {
+    int64_t zs, text;
+    return (formats & SDSJ_FORMAT_PNG_META) && png_meta_stream(rd, tag, p, p + (int64_t)len, &zs, &text) != 0;
+  }
+  // acTL (APNG), unknown critical chunks: PIL decides; so it does for eXIf and the ancillary chunks it
+  // has no handler for unless the mask has SDSJ_FORMAT_PNG_EXT
+  bool letters = true;
+  for (int k = 0; k < 4; k++) {
+    const int c = (int)((tag >> (8 * k)) & 255u) | 32;
+    letters = letters && c >= 'a' && c <= 'z';
+  }
+  const bool handled = tag == png_tag('a', 'c', 'T', 'L') || tag == png_tag('f', 'c', 'T', 'L') ||
+                       tag == png_tag('f', 'd', 'A', 'T') || tag == png_tag('t', 'R', 'N', 'S');  // (tRNS: png_parse's own rule)
+  return (formats & SDSJ_FORMAT_PNG_EXT) && letters && ((tag >> 29) & 1u) && !handled;
+}
+
 // Signature, IHDR, the chunks before the first IDAT.  Image.open reads exactly these chunks and
 // verifies the CRC of each (PngImagePlugin.py ChunkStream.crc), so a mismatch in any of them is an
 // error there; a chunk whose handler could raise or that this path has not been checked against
-// (iCCP, zTXt, iTXt, acTL, ... and unknown ones) hands the sample over instead of guessing.
+// (acTL, unknown ones, ... and iCCP, zTXt, iTXt without SDSJ_FORMAT_PNG_META) hands the sample over
+// instead of guessing.
 // h's IHDR fields are filled as soon as IHDR has been read, whatever the status.
 //
 // formats with SDSJ_FORMAT_PNG_EXT: Adam7 files and every legal (colour type, depth) pair are accepted,
@@ -152,6 +240,11 @@ SDSJ_HD inline bool png_signature(const Reader& rd, int64_t n) {
 // :490, tRNS :498, gAMA :521, cHRM :528, sRGB :538, pHYs :555, tEXt :573, zTXt :593, iTXt :628, eXIf
 // :671, acTL :678, fcTL :699, fdAT :729.  eXIf's only stores the bytes (:671-675) and is accepted too;
 // iCCP, zTXt and iTXt inflate data and can raise, the APNG chunks change what is decoded: PIL decides.
+//
+// formats with SDSJ_FORMAT_PNG_META: iCCP, zTXt and iTXt are accepted here by their structure and CRC
+// (png_chunk_ok, png_meta_stream); their zlib streams, the text budget and the chunks after the image data
+// are png_meta_check's, which the caller runs on a sample this function accepted (k_png_meta on the
+// device, host_png_meta for host planning and the probe).
 template <class Reader>
 SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h, int formats = SDSJ_FORMAT_PNG) {
   const bool ext = (formats & SDSJ_FORMAT_PNG_EXT) != 0;
@@ -195,28 +288,8 @@ SDSJ_HD int png_parse(const Reader& rd, int64_t n, PngHdr* h, int formats = SDSJ
       h->plte_pos = p + 8;
     } else if (tag == png_tag('t', 'R', 'N', 'S')) {  // ignored by convert("RGB"); its handler indexes by colour type
       if (len > 256 || (h->ctype == 0 && len != 2) || (h->ctype == 2 && len != 6)) return SDSJ_UNSUPPORTED;
-    } else if (tag == png_tag('g', 'A', 'M', 'A')) {
-      if (len != 4) return SDSJ_UNSUPPORTED;
-    } else if (tag == png_tag('c', 'H', 'R', 'M')) {
-      if (len != 32) return SDSJ_UNSUPPORTED;
-    } else if (tag == png_tag('s', 'R', 'G', 'B')) {
-      if (len != 1) return SDSJ_UNSUPPORTED;
-    } else if (tag == png_tag('p', 'H', 'Y', 's')) {
-      if (len != 9) return SDSJ_UNSUPPORTED;
-    } else if (tag == png_tag('t', 'E', 'X', 't')) {
-      if (len > 65536) return SDSJ_UNSUPPORTED;
-    } else {
-      // acTL (APNG), iCCP, zTXt, iTXt, unknown critical chunks: PIL decides; so it does for eXIf and the
-      // ancillary chunks it has no handler for unless the mask has SDSJ_FORMAT_PNG_EXT
-      bool letters = true;
-      for (int k = 0; k < 4; k++) {
-        const int c = (int)((tag >> (8 * k)) & 255u) | 32;
-        letters = letters && c >= 'a' && c <= 'z';
-      }
-      const bool handled = tag == png_tag('i', 'C', 'C', 'P') || tag == png_tag('z', 'T', 'X', 't') ||
-                           tag == png_tag('i', 'T', 'X', 't') || tag == png_tag('a', 'c', 'T', 'L') ||
-                           tag == png_tag('f', 'c', 'T', 'L') || tag == png_tag('f', 'd', 'A', 'T');
-      if (!ext || !letters || !((tag >> 29) & 1u) || handled) return SDSJ_UNSUPPORTED;
+    } else if (!png_chunk_ok(rd, tag, p + 8, len, formats)) {
+      return SDSJ_UNSUPPORTED;
     }
     p += 12 + (int64_t)len;
   }
@@ -545,7 +618,9 @@ SDSJ_HDI bool zlib_header(PngBits<Reader>& b, int* window) {
 //   out.match(dist, len)   appends len bytes copied from dist bytes back (overlap allowed)
 // The sink never sees a byte beyond `expect` or a source before the first byte: both end the image
 // here.  Returns SDSJ_OK when the stream is well formed, ends in a final block and produced exactly
-// `expect` bytes; *adler = the trailer's value (the caller compares it with the output's).
+// `expect` bytes; *adler = the trailer's value (the caller compares it with the output's).  SDSJ_UNSUPPORTED
+// is png_tail_ok's answer alone, *adler being set: a caller for whom png_meta_check has judged what follows
+// the image data takes it for SDSJ_OK (k_png_inflate_meta).
 template <class Reader, class Sink>
 SDSJ_HDI int png_inflate(PngBits<Reader>& b, InfTables* T, Sink& out, int64_t expect, uint32_t* adler) {
   int window = 0;
@@ -591,6 +666,119 @@ SDSJ_HDI int png_inflate(PngBits<Reader>& b, InfTables* T, Sink& out, int64_t ex
   *adler = ((v & 0xFF) << 24) | ((v & 0xFF00) << 8) | ((v >> 8) & 0xFF00) | (v >> 24);
   if (!png_tail_ok(b)) return SDSJ_UNSUPPORTED;
   return SDSJ_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// SDSJ_FORMAT_PNG_META: the size rule, the text budget and the chunks after the image data.
+// ------------------------------------------------------------------------------------------
+// A bit reader confined to one chunk's payload [p, e): no hop to a next chunk.
+template <class Reader>
+SDSJ_HDI void png_bits_span(PngBits<Reader>& b, const Reader& rd, int64_t n, int64_t p, int64_t e) {
+  b.rd = rd;
+  b.n = n;
+  b.buf = 0;
+  b.cnt = 0;
+  b.ended = 1;
+  b.pos = p;
+  b.chunk_end = e;
+}
+
+// The size rule: the zlib stream inflated without output or window.  True iff it is well formed up to the
+// end of a final block and produces fewer than kPngMaxTextChunk bytes (*count).  zlib then produces no
+// more than that either -- it decodes the same symbols, and stops earlier where it also checks what is
+// not checked here (match distances, the Adler-32) -- so _safe_zlib_decompress cannot raise.  Everything
+// else is refused, including the malformed streams whose zlib.error PIL swallows.
+template <class Reader>
+SDSJ_HDI bool png_inflate_count(PngBits<Reader>& b, InfTables* T, int64_t* count) {
+  int window = 0;
+  if (!zlib_header(b, &window)) return false;
+  int64_t produced = 0;
+  for (;;) {
+    int final = 0, type = 0, stored = 0;
+    if (!inf_block_header(b, T, &final, &type, &stored)) return false;
+    if (type == 0) {
+      produced += stored;
+      // the buffered whole bytes first, the rest by position (the reader is confined to its payload)
+      const int have = b.cnt >> 3, drop = stored < have ? stored : have;
+      b.buf = drop < 8 ? b.buf >> (8 * drop) : 0;
+      b.cnt -= 8 * drop;
+      const int64_t rest = stored - drop;
+      if (rest > b.chunk_end - b.pos) return false;
+      b.pos += rest;
+    } else {
+      for (;;) {
+        const int s = inf_decode(b, &T->ll, T->ll_sym);
+        if (s < 0) return false;
+        if (s == 256) break;
+        int len = 1, dist = 0;
+        if (s > 256 && (!inf_length(b, s, &len) || !inf_distance(b, T, &dist))) return false;
+        produced += len;
+        if (produced >= kPngMaxTextChunk) return false;
+      }
+    }
+    if (produced >= kPngMaxTextChunk) return false;
+    if (final) break;
+  }
+  *count = produced;
+  return true;
+}
+
+// One chunk png_chunk_ok accepted, payload [p, p + len) inside the input: its share of the text budget
+// (tEXt: its payload, an upper bound of the value's length) and, for iCCP / zTXt / iTXt, the size rule.
+template <class Reader>
+SDSJ_HDI bool png_meta_chunk(Reader& rd, int64_t n, uint32_t tag, int64_t p, uint32_t len, InfTables* T, int64_t* budget) {
+  if (tag == png_tag('t', 'E', 'X', 't')) {
+    *budget += (int64_t)len;
+  } else if (tag == png_tag('i', 'C', 'C', 'P') || tag == png_tag('z', 'T', 'X', 't') || tag == png_tag('i', 'T', 'X', 't')) {
+    int64_t zs = 0, text = 0;
+    const int kind = png_meta_stream(rd, tag, p, p + (int64_t)len, &zs, &text);
+    if (kind == 0) return false;
+    if (kind == 1) {
+      *budget += text;
+    } else {
+      PngBits<Reader> b;
+      png_bits_span(b, rd, n, zs, p + (int64_t)len);
+      int64_t count = 0;
+      const bool ok = png_inflate_count(b, T, &count);
+      rd = b.rd;  // (a reader with state, the device's LDS window: the copy has moved it)
+      if (!ok) return false;
+      if (text) *budget += count;
+    }
+  }
+  return *budget <= kPngMaxTextMemory;
+}
+
+// With SDSJ_FORMAT_PNG_META, after png_parse accepted the sample (idat_pos: its first IDAT): the size rule
+// and the text budget over the chunks before the image data, then the chunks after it as load_end
+// (PngImagePlugin.py:1024) walks them -- no CRC is checked there -- under the rule of the same mask
+// (png_chunk_ok) and the same budget.  The image data ends with the run of IDAT chunks (PIL skips those the
+// zlib stream did not need); the walk ends at IEND or where no chunk header is left after a CRC.  PLTE, tRNS,
+// IHDR, an IDAT after another chunk, the APNG chunks, critical and non-letter types, a payload that leaves
+// the input and a tail longer than kPngMaxHeader stay with PIL.  SDSJ_OK or SDSJ_UNSUPPORTED; no byte
+// outside [0, n) is read.
+template <class Reader>
+SDSJ_HDI int png_meta_check(Reader rd, int64_t n, int64_t idat_pos, int formats, InfTables* T) {
+  int64_t budget = 0;
+  int64_t p = 8;
+  int64_t tail0 = -1;  // the first chunk after the IDAT run
+  for (;;) {
+    if (p + 8 > n) return SDSJ_OK;  // the input ends: PIL stops on the short read
+    const uint32_t len = png_be32(rd, p), tag = png_be32(rd, p + 4);
+    const int64_t e = p + 8 + (int64_t)len;
+    if (p >= idat_pos) {  // (before it png_parse has applied png_chunk_ok, and every chunk lies inside the input)
+      if (tag == png_tag('I', 'E', 'N', 'D')) return len == 0 ? SDSJ_OK : SDSJ_UNSUPPORTED;
+      if (tail0 < 0 && tag == png_tag('I', 'D', 'A', 'T')) {
+        if (len > 0x7FFFFFFFu || e > n) return SDSJ_UNSUPPORTED;
+        p = e + 4;
+        continue;
+      }
+      if (tail0 < 0) tail0 = p;
+      if (p - tail0 > kPngMaxHeader || len > (uint32_t)kPngMaxHeader || e > n) return SDSJ_UNSUPPORTED;
+      if (!png_chunk_ok(rd, tag, p + 8, len, formats)) return SDSJ_UNSUPPORTED;
+    }
+    if (!png_meta_chunk(rd, n, tag, p + 8, len, T, &budget)) return SDSJ_UNSUPPORTED;
+    p = e + 4;
+  }
 }
 
 constexpr uint32_t kAdlerMod = 65521;

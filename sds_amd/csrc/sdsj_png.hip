@@ -5,7 +5,9 @@
 //   k_png_unfilter  one wavefront per image: filters 0-4 reversed, RGB rows written to off_rgb (gray
 //                   replicated, palette looked up, alpha dropped), which k_hpass / k_vpass then read
 // With SDSJ_FORMAT_PNG_EXT in the mask launch_png takes k_png_inflate_ext and adds k_png_unfilter_ext
-// (sdsj_png_ext.hip) for what k_png_unfilter skips: Adam7 files and bit depths 1, 2, 4, 16.
+// (sdsj_png_ext.hip) for what k_png_unfilter skips: Adam7 files and bit depths 1, 2, 4, 16.  With
+// SDSJ_FORMAT_PNG_META it takes k_png_inflate_meta (sdsj_png_meta.hip), after k_png_meta has judged the
+// compressed chunks and what follows the image data.
 //
 // Reference behaviour: PIL.Image.open(...).convert("RGB").  Every correctness and bounds decision is
 // taken by the shared functions of sdsj_png.h (the same ones the sanitizer driver runs serially on
@@ -136,7 +138,8 @@ hipError_t launch_png(int n, ImgDesc* descs, const uint8_t* blob, const int64_t*
   }
   const unsigned g = route_grid(hint, kRtPng, n);
   const bool ext = (formats & SDSJ_FORMAT_PNG_EXT) != 0;
-  if (ext) launch_png_inflate_ext(g, descs, blob, offsets, lengths, scratch, routes, cap, s);
+  if (formats & SDSJ_FORMAT_PNG_META) launch_png_inflate_meta(g, descs, blob, offsets, lengths, scratch, routes, cap, s);
+  else if (ext) launch_png_inflate_ext(g, descs, blob, offsets, lengths, scratch, routes, cap, s);
   else hipLaunchKernelGGL(k_png_inflate, dim3(g), dim3(64), 0, s, descs, blob, offsets, lengths, scratch, routes, cap);
   if (between) (void)hipEventRecord(between, s);
   hipLaunchKernelGGL(k_png_unfilter, dim3(g), dim3(64), 0, s, descs, blob, offsets, scratch, routes, cap);
@@ -155,7 +158,8 @@ extern "C" int sdsj_png_probe_formats(const uint8_t* png, size_t n, int formats,
   memset(out, 0, sizeof(*out));
   sdsj::PngHdr h;
   const sdsj::GlobalReader rd{png};
-  const int st = sdsj::png_parse(rd, (int64_t)n, &h, formats);
+  int st = sdsj::png_parse(rd, (int64_t)n, &h, formats);
+  if (st == SDSJ_OK && (formats & SDSJ_FORMAT_PNG_META)) st = sdsj::host_png_meta(png, (int64_t)n, h.idat_pos, formats);
   out->width = h.width;
   out->height = h.height;
   out->bit_depth = h.bit_depth;

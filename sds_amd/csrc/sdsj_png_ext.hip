@@ -17,20 +17,6 @@ namespace sdsj {
 
 namespace {
 
-// A filter type above 4 in the first byte of any row of any pass, lane l looking at rows l, l + 64, ...
-// (not inlined: the walk over the passes stays out of k_png_inflate's register budget).  Only
-// k_png_inflate_ext calls it: engines without SDSJ_FORMAT_PNG_EXT keep the kernel without the walk.
-__device__ __noinline__ bool wave_filter_bytes_bad(const uint8_t* out, int w, int h, int ctype, PngIhdr ih, int lane) {
-  bool bad = false;
-  for (int p = 0; p < (ih.interlace ? 7 : 1); p++) {
-    PngPass ps;
-    if (!png_pass_at(w, h, ctype, ih.depth, ih.interlace, p, &ps)) continue;
-    const int64_t pitch = 1 + ps.rowbytes;
-    for (int y = lane; y < ps.h; y += 64) bad |= out[ps.off + (int64_t)y * pitch] > 4;
-  }
-  return bad;
-}
-
 // k_png_inflate (sdsj_png.hip) with the filter-byte check over the rows of every pass.
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_png_inflate_ext(ImgDesc* __restrict__ descs, const uint8_t* __restrict__ blob,
                                                    const int64_t* __restrict__ offsets,

@@ -124,6 +124,20 @@ __device__ uint32_t wave_adler(const uint8_t* p, int64_t n, int lane) {
   return (S2 << 16) | S1;
 }
 
+// A filter type above 4 in the first byte of any row of any pass, lane l looking at rows l, l + 64, ...
+// (not inlined: the walk over the passes stays out of k_png_inflate's register budget).  Only
+// k_png_inflate_ext and k_png_inflate_meta call it: engines with the base mask keep the kernel without the walk.
+__device__ __noinline__ bool wave_filter_bytes_bad(const uint8_t* out, int w, int h, int ctype, PngIhdr ih, int lane) {
+  bool bad = false;
+  for (int p = 0; p < (ih.interlace ? 7 : 1); p++) {
+    PngPass ps;
+    if (!png_pass_at(w, h, ctype, ih.depth, ih.interlace, p, &ps)) continue;
+    const int64_t pitch = 1 + ps.rowbytes;
+    for (int y = lane; y < ps.h; y += 64) bad |= out[ps.off + (int64_t)y * pitch] > 4;
+  }
+  return bad;
+}
+
 }  // namespace
 
 }  // namespace sdsj

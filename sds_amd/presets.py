@@ -194,7 +194,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     reaching the parent through HIP IPC); a string = the address of a running service.
 
     ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` /
-    ``"png"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    ``"png"`` / ``"png-ext"`` / ``"png-meta"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
@@ -203,6 +203,13 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     16 and files with tIME / bKGD / sBIT / eXIf or private ancillary chunks; APNG and files with iCCP, zTXt
     or iTXt chunks still rerun on PIL.  Under ``"png-ext"`` the inflate kernel also walks the pass layout, which
     measured 2 % slower on plain 8-bit files (6.18k against 6.32k images/s, ``profiles/png_ext_bench.jsonl``): a shard of those alone is better served by ``"png"``.
+    ``"png-meta"`` (it includes ``"png"`` too and combines with ``"png-ext"``) takes files as converters and editors
+    write them: with an ICC profile (iCCP -- Pillow writes one whenever the source image carried one), zTXt / iTXt
+    text such as an XMP packet, and chunks after the image data (tEXt, gAMA, cHRM, sRGB, pHYs, the three above;
+    with ``"png-ext"`` also tIME and the like).  None of them changes a pixel.  Files on which PIL raises (a
+    compressed chunk that inflates to more than 1 MiB, more than 64 MiB of text) and compressed chunks whose zlib
+    stream is damaged still rerun on PIL.  Plain files decode 9 % slower under this mask than under ``"png"`` (5.9k
+    against 6.5k images/s, ``profiles/png_meta_bench.jsonl``), files with such chunks at 5.6k against 0.31k on PIL.
     In a served worker process (the decode service) PNG samples keep the PIL route whatever this says: the
     service's wire protocol carries no format mask.
     """
@@ -543,7 +550,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"png"`` or ``"png-ext"`` to opt in; see GpuDecodeResizeImageTransform).
+    formats decoded natively (add ``"png"``, ``"png-ext"`` or ``"png-meta"`` to opt in; see GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
     the pipeline gets device tensors (it decodes in-process), while its forked DataLoader workers get

@@ -13,7 +13,12 @@ engine's stage times (png_inflate / png_unfilter among them).  `python tools/png
 `--ext` measures the wider subset instead (formats=("jpeg", "png-ext"), k_png_unfilter_ext): the same 64
 images as Adam7-interlaced RGB (written by tests/png_ext_synth.py, Pillow writes no interlaced files) and as
 4-bit palette files (Pillow's quantize to 16 colours, bits=4), after the base pool itself under the full mask;
-every line then carries a "case"."""
+every line then carries a "case".
+
+`--meta` measures files as editors write them (formats=("jpeg", "png-meta"), k_png_meta): the base pool re-saved
+through Pillow with an ICC profile of about 3 KB (arbitrary bytes: Pillow does not parse them), a compressed iTXt
+XMP-like packet of about 4 KB and a tEXt appended after the image data, after the base pool itself under that
+mask; the "parse" stage holds k_parse (now with the CRC of the profile) and k_png_meta."""
 import io
 import json
 import os
@@ -25,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 BOTH = ("jpeg", "png")
 EXT = ("jpeg", "png-ext")
+META = ("jpeg", "png-meta")
 
 
 def make_pool():
@@ -56,6 +62,28 @@ def make_ext_pools():
         Image.fromarray(rgb).quantize(16).save(b, "PNG", bits=4)
         pal4.append(b.getvalue())
     return [("adam7 RGB", adam7), ("4-bit palette", pal4)]
+
+
+def make_meta_pool():
+    import numpy as np
+    from PIL import Image
+    from PIL.PngImagePlugin import PngInfo
+
+    from tests import png_synth as S
+    from tests.golden.synth import synth_rgb
+    pool = []
+    for i in range(64):
+        rng = np.random.default_rng(1234 + i)
+        rgb = synth_rgb(rng, 640, 480)
+        info = PngInfo()
+        info.add_itxt("XML:com.adobe.xmp", "<x:xmpmeta>" + "".join(f"<rdf:li>{int(v)}</rdf:li>" for v in rng.integers(0, 1 << 30, 200))
+                      + "</x:xmpmeta>", zip=True)
+        b = io.BytesIO()
+        Image.fromarray(rgb).save(b, "PNG", icc_profile=rng.integers(0, 256, 3000, dtype=np.uint8).tobytes(), pnginfo=info)
+        data = b.getvalue()
+        k = data.rindex(b"IEND") - 4
+        pool.append(data[:k] + S.chunk(b"tEXt", b"Comment\0written after the image data") + data[k:])
+    return pool
 
 
 def native(pool, n, formats=BOTH, case=None):
@@ -152,15 +180,18 @@ def latency(pool, n, formats=BOTH, case=None):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--ext"]
-    ext = "--ext" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a not in ("--ext", "--meta")]
+    ext, meta = "--ext" in sys.argv[1:], "--meta" in sys.argv[1:]
     n = int(args[0]) if args else 4096
     routes = args[1:] or ["native", "fallback", "latency"]
     # (--ext: the base pool too, so that what the full mask costs plain 8-bit files is on record)
-    pools = [("RGB under png-ext", make_pool())] + make_ext_pools() if ext else [(None, make_pool())]
+    if meta:
+        pools = [("RGB under png-meta", make_pool()), ("RGB with iCCP, iTXt and a trailing tEXt", make_meta_pool())]
+    else:
+        pools = [("RGB under png-ext", make_pool())] + make_ext_pools() if ext else [(None, make_pool())]
     for case, pool in pools:
         for r in routes:
-            {"native": native, "fallback": fallback, "latency": latency}[r](pool, n, EXT if ext else BOTH, case)
+            {"native": native, "fallback": fallback, "latency": latency}[r](pool, n, META if meta else EXT if ext else BOTH, case)
 
 
 if __name__ == "__main__":
