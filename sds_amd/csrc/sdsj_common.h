@@ -219,12 +219,12 @@ struct ImgDesc {
   int8_t mh;  // latency mode: the multi-hypothesis speculative pass (k_entspec_mh) takes the image
   int8_t sm_pad[3];
   int32_t etab;  // k_enttab: the image whose EntTables it decodes with (itself, or image 0 of the lane when equal)
-  int32_t etab_pad;  // PNG samples: IHDR's bit depth | interlace method << 8 (png_fill_desc); otherwise unused
+  int32_t png_depth_lace;  // PNG samples: IHDR's bit depth | interlace method << 8 (png_fill_desc); otherwise unused
   // PNG sample (sdsj_png.h png_parse; engines with SDSJ_FORMAT_PNG enabled): no components or entropy
   // data; k_png_inflate fills the scanline buffer at off_png (png_raw bytes: height x (1 + width x
   // png_bpp); with SDSJ_FORMAT_PNG_EXT the sum of png_layout's passes, png_bpp being the filter unit)
   // from the IDAT chain at png_idat_pos, k_png_unfilter / k_png_unfilter_ext write the RGB rows at
-  // off_rgb.  Bit depth and interlace travel in etab_pad (the struct's size and offsets are pinned).
+  // off_rgb.  Bit depth and interlace travel in png_depth_lace (the struct's size and offsets are pinned).
   int32_t png;
   int32_t png_ctype, png_bpp, png_plte_n;  // colour type, filter unit (bytes per pixel, 1 below depth 8), PLTE entries
   int64_t png_plte_pos, png_idat_pos;      // relative to the sample's first byte

@@ -26,8 +26,8 @@ inline unsigned route_grid(uint64_t hint, int r, int64_t full) {
 hipError_t launch_parse(int n, const uint8_t* blob, int64_t blob_bytes, const int64_t* offsets, const int32_t* lengths,
                         const sdsj_op& op, int warm_bits, bool small, ImgDesc* descs, ImgTables* tables, hipStream_t s,
                         int formats = SDSJ_FORMAT_JPEG);
-// PNG samples (route kRtPng): k_png_inflate then k_png_unfilter and, when `formats` has
-// SDSJ_FORMAT_PNG_EXT, k_png_unfilter_ext (sdsj_png.hip); `between` (optional) is
+// PNG samples (route kRtPng): k_png_inflate then k_png_unfilter (sdsj_png.hip) and, when `formats` has
+// SDSJ_FORMAT_PNG_EXT, k_png_unfilter_ext (sdsj_png_ext.hip); `between` (optional) is
 // recorded between the two
 hipError_t launch_png(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                       uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,

@@ -879,7 +879,7 @@ SDSJ_HD inline void png_fill_desc(ImgDesc* d, const PngHdr& h) {
   // (a header png_parse refused may hold any sizes: nothing reads png_raw then)
   if (h.bit_depth == 8 && !h.interlace) d->png_raw = png_raw_bytes(h.width, h.height, h.bpp);
   else d->png_raw = h.width <= 65535 && h.height <= 65535 ? png_layout_bytes(h.width, h.height, h.ctype, h.bit_depth, h.interlace) : 0;
-  d->etab_pad = (h.bit_depth & 255) | ((h.interlace & 255) << 8);  // (padding the struct already had: its size is pinned)
+  d->png_depth_lace = (h.bit_depth & 255) | ((h.interlace & 255) << 8);  // (the struct's size and offsets are pinned)
   d->off_png = 0;
 }
 

@@ -2,7 +2,8 @@
 //
 //   k_png_inflate   one wavefront per image: zlib / deflate over the IDAT chain into the image's
 //                   scanline buffer (scratch, off_png), Adler-32 and the rows' filter bytes checked
-//   k_png_unfilter  one wavefront per image: filters 0-4 reversed, RGB rows written to off_rgb (gray
+//                   (sdsj_png_inflate_kernel.h, the one source of the three masks' inflate kernels)
+//   k_png_unfilter one wavefront per image: filters 0-4 reversed, RGB rows written to off_rgb (gray
 //                   replicated, palette looked up, alpha dropped), which k_hpass / k_vpass then read
 // With SDSJ_FORMAT_PNG_EXT in the mask launch_png takes k_png_inflate_ext and adds k_png_unfilter_ext
 // (sdsj_png_ext.hip) for what k_png_unfilter skips: Adam7 files and bit depths 1, 2, 4, 16.  With
@@ -25,43 +26,11 @@ namespace sdsj {
 
 namespace {
 
-// (k_png_inflate_ext of sdsj_png_ext.hip is this kernel with the filter-byte check over every pass: written
-// out twice, in two translation units, because that leaves this one's machine code what it was before the
-// wider subset existed -- as a shared inlined body it compiled differently, and the batch ran 0.8 % slower.)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_png_inflate(ImgDesc* __restrict__ descs, const uint8_t* __restrict__ blob,
-                                                   const int64_t* __restrict__ offsets,
-                                                   const int32_t* __restrict__ lengths, uint8_t* scratch,
-                                                   const int32_t* __restrict__ routes, int cap) {
-  __shared__ InfTables T;
-  __shared__ uint8_t win[kWin];
-  const int32_t* rl = route_list(routes, cap, kRtPng);
-  const int lane = threadIdx.x;
-  for (int li = blockIdx.x; li < routes[kRtPng]; li += gridDim.x) {
-    const int img = rl[li];
-    ImgDesc* d = &descs[img];
-    if (d->status != SDSJ_OK || !d->png) continue;
-    const WindowReader rd{blob + offsets[img], (int64_t)lengths[img], win, lane, -(int64_t)4 * kWin};
-    const int64_t expect = d->png_raw;
-    uint8_t* out = scratch + d->off_png;
-    PngBits<WindowReader> br;
-    png_bits_init(br, rd, rd.n, d->png_idat_pos);
-    WaveSink sink{out, 0, 0, 0u, lane};
-    uint32_t want = 0;
-    int st = png_inflate(br, &T, sink, expect, &want);
-    sink.flush();
-    wave_store_fence();
-    if (st == SDSJ_OK) {
-      if (wave_adler(out, expect, lane) != want) st = SDSJ_CORRUPT;
-      // a filter type above 4 is an error in ZipDecode.c: the first byte of every row
-      const int64_t pitch = 1 + (int64_t)d->width * d->png_bpp;
-      bool bad = false;
-      for (int y = lane; y < d->height; y += 64) bad |= out[(int64_t)y * pitch] > 4;
-      if (__ballot(bad)) st = SDSJ_CORRUPT;
-    }
-    __syncthreads();  // T is rebuilt by the next image
-    if (st != SDSJ_OK && lane == 0) d->status = st;
-  }
-}
+// k_png_inflate: the shared kernel with the filter-byte check over the rows of one plain image.
+#define SDSJ_PNG_INFLATE_KERNEL k_png_inflate
+#define SDSJ_PNG_INFLATE_PASSES 0
+#define SDSJ_PNG_INFLATE_TAIL_JUDGED 0
+#include "sdsj_png_inflate_kernel.h"
 
 
 // Skewed wavefront over bands of 64 rows: lane j reconstructs row base + j and runs j pixels behind

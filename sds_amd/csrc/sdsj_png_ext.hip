@@ -2,6 +2,7 @@
 // depths 1, 2, 4, 16), launched by launch_png (sdsj_png.hip) only when the engine's mask has the bit.
 //
 //   k_png_inflate_ext   k_png_inflate with the filter-byte check walking the rows of every pass
+//                       (sdsj_png_inflate_kernel.h)
 //   k_png_unfilter_ext  one wavefront per (image, pass) for what k_png_unfilter skips
 //
 // A translation unit of its own: the base subset's kernels are compiled exactly as without it.
@@ -17,38 +18,11 @@ namespace sdsj {
 
 namespace {
 
-// k_png_inflate (sdsj_png.hip) with the filter-byte check over the rows of every pass.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_png_inflate_ext(ImgDesc* __restrict__ descs, const uint8_t* __restrict__ blob,
-                                                   const int64_t* __restrict__ offsets,
-                                                   const int32_t* __restrict__ lengths, uint8_t* scratch,
-                                                   const int32_t* __restrict__ routes, int cap) {
-  __shared__ InfTables T;
-  __shared__ uint8_t win[kWin];
-  const int32_t* rl = route_list(routes, cap, kRtPng);
-  const int lane = threadIdx.x;
-  for (int li = blockIdx.x; li < routes[kRtPng]; li += gridDim.x) {
-    const int img = rl[li];
-    ImgDesc* d = &descs[img];
-    if (d->status != SDSJ_OK || !d->png) continue;
-    const WindowReader rd{blob + offsets[img], (int64_t)lengths[img], win, lane, -(int64_t)4 * kWin};
-    const int64_t expect = d->png_raw;
-    uint8_t* out = scratch + d->off_png;
-    PngBits<WindowReader> br;
-    png_bits_init(br, rd, rd.n, d->png_idat_pos);
-    WaveSink sink{out, 0, 0, 0u, lane};
-    uint32_t want = 0;
-    int st = png_inflate(br, &T, sink, expect, &want);
-    sink.flush();
-    wave_store_fence();
-    if (st == SDSJ_OK) {
-      if (wave_adler(out, expect, lane) != want) st = SDSJ_CORRUPT;
-      // a filter type above 4 is an error in ZipDecode.c: the first byte of every row (of every pass)
-      if (__ballot(wave_filter_bytes_bad(out, d->width, d->height, d->png_ctype, png_ihdr(d), lane))) st = SDSJ_CORRUPT;
-    }
-    __syncthreads();  // T is rebuilt by the next image
-    if (st != SDSJ_OK && lane == 0) d->status = st;
-  }
-}
+// k_png_inflate_ext: the shared kernel with the filter-byte check over the rows of every pass.
+#define SDSJ_PNG_INFLATE_KERNEL k_png_inflate_ext
+#define SDSJ_PNG_INFLATE_PASSES 1
+#define SDSJ_PNG_INFLATE_TAIL_JUDGED 0
+#include "sdsj_png_inflate_kernel.h"
 
 
 // What k_png_unfilter skips, one wavefront per (image, pass): the passes of an Adam7 image are

@@ -8,7 +8,7 @@
 //                       the scratch need are those of host planning (host_png_meta runs the same function).
 //   k_png_inflate_meta  k_png_inflate_ext that ignores the strict answer of png_tail_ok, which k_png_meta has
 //                       replaced; it serves the mask with and without SDSJ_FORMAT_PNG_EXT (the walk over
-//                       the passes of a plain image is the check of its rows).
+//                       the passes of a plain image is the check of its rows) (sdsj_png_inflate_kernel.h).
 //
 // A translation unit of its own: the kernels of the other masks are compiled exactly as without it.
 #include <hip/hip_runtime.h>
@@ -23,39 +23,11 @@ namespace sdsj {
 
 namespace {
 
-// k_png_inflate_ext (sdsj_png_ext.hip) for which png_tail_ok's refusal does not count: the tail is k_png_meta's.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_png_inflate_meta(ImgDesc* __restrict__ descs, const uint8_t* __restrict__ blob,
-                                                   const int64_t* __restrict__ offsets,
-                                                   const int32_t* __restrict__ lengths, uint8_t* scratch,
-                                                   const int32_t* __restrict__ routes, int cap) {
-  __shared__ InfTables T;
-  __shared__ uint8_t win[kWin];
-  const int32_t* rl = route_list(routes, cap, kRtPng);
-  const int lane = threadIdx.x;
-  for (int li = blockIdx.x; li < routes[kRtPng]; li += gridDim.x) {
-    const int img = rl[li];
-    ImgDesc* d = &descs[img];
-    if (d->status != SDSJ_OK || !d->png) continue;
-    const WindowReader rd{blob + offsets[img], (int64_t)lengths[img], win, lane, -(int64_t)4 * kWin};
-    const int64_t expect = d->png_raw;
-    uint8_t* out = scratch + d->off_png;
-    PngBits<WindowReader> br;
-    png_bits_init(br, rd, rd.n, d->png_idat_pos);
-    WaveSink sink{out, 0, 0, 0u, lane};
-    uint32_t want = 0;
-    int st = png_inflate(br, &T, sink, expect, &want);
-    if (st == SDSJ_UNSUPPORTED) st = SDSJ_OK;  // png_tail_ok's strict answer: k_png_meta has judged the tail under the mask
-    sink.flush();
-    wave_store_fence();
-    if (st == SDSJ_OK) {
-      if (wave_adler(out, expect, lane) != want) st = SDSJ_CORRUPT;
-      // a filter type above 4 is an error in ZipDecode.c: the first byte of every row (of every pass)
-      if (__ballot(wave_filter_bytes_bad(out, d->width, d->height, d->png_ctype, png_ihdr(d), lane))) st = SDSJ_CORRUPT;
-    }
-    __syncthreads();  // T is rebuilt by the next image
-    if (st != SDSJ_OK && lane == 0) d->status = st;
-  }
-}
+// k_png_inflate_meta: k_png_inflate_ext for which png_tail_ok's refusal does not count: the tail is k_png_meta's.
+#define SDSJ_PNG_INFLATE_KERNEL k_png_inflate_meta
+#define SDSJ_PNG_INFLATE_PASSES 1
+#define SDSJ_PNG_INFLATE_TAIL_JUDGED 1
+#include "sdsj_png_inflate_kernel.h"
 
 // The chunk bytes come through the LDS window, the tables of the count-only inflate sit in LDS, and the
 // walk is wave-uniform: every lane holds the same state and takes the same branches (the window's

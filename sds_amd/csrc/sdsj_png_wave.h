@@ -1,5 +1,6 @@
-// sdsj_png_wave.h -- the wavefront-level pieces the PNG kernels of sdsj_png.hip (base subset) and
-// sdsj_png_ext.hip (SDSJ_FORMAT_PNG_EXT) share: readers, the inflate sink, Adler-32.  Device code only; every correctness decision is in sdsj_png.h.
+// sdsj_png_wave.h -- the wavefront-level pieces the PNG kernels of sdsj_png.hip (base subset),
+// sdsj_png_ext.hip (SDSJ_FORMAT_PNG_EXT) and sdsj_png_meta.hip (SDSJ_FORMAT_PNG_META) share: readers, the
+// inflate sink, Adler-32.  Device code only; every correctness decision is in sdsj_png.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,12 +43,12 @@ struct WindowReader {
   }
 };
 
-// Bit depth and interlace method of a PNG descriptor (png_fill_desc keeps them in etab_pad).
+// Bit depth and interlace method of a PNG descriptor (png_fill_desc keeps them in png_depth_lace).
 struct PngIhdr {
   int depth, interlace;
 };
-__device__ __forceinline__ PngIhdr png_ihdr(const ImgDesc* d) { return PngIhdr{d->etab_pad & 255, (d->etab_pad >> 8) & 255}; }
-__device__ __forceinline__ bool png_plain(const ImgDesc* d) { return d->etab_pad == 8; }  // depth 8, not interlaced
+__device__ __forceinline__ PngIhdr png_ihdr(const ImgDesc* d) { return PngIhdr{d->png_depth_lace & 255, (d->png_depth_lace >> 8) & 255}; }
+__device__ __forceinline__ bool png_plain(const ImgDesc* d) { return d->png_depth_lace == 8; }  // depth 8, not interlaced
 
 // Stores of this wave must have completed before its later loads of the same bytes (match sources,
 // the Adler pass, the previous band's last row): a workgroup-scope release / acquire pair, which on
@@ -125,8 +126,8 @@ __device__ uint32_t wave_adler(const uint8_t* p, int64_t n, int lane) {
 }
 
 // A filter type above 4 in the first byte of any row of any pass, lane l looking at rows l, l + 64, ...
-// (not inlined: the walk over the passes stays out of k_png_inflate's register budget).  Only
-// k_png_inflate_ext and k_png_inflate_meta call it: engines with the base mask keep the kernel without the walk.
+// (not inlined: the walk over the passes stays out of the inflate kernel's register budget;
+// sdsj_png_inflate_kernel.h says which kernels call it).
 __device__ __noinline__ bool wave_filter_bytes_bad(const uint8_t* out, int w, int h, int ctype, PngIhdr ih, int lane) {
   bool bad = false;
   for (int p = 0; p < (ih.interlace ? 7 : 1); p++) {

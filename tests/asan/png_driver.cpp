@@ -4,31 +4,7 @@
 // RGB -- reads records [u32 length][bytes] from the file in argv[1] and prints one line per record:
 // status width height fnv1a64(RGB).  Each input, each scanline buffer and each RGB buffer is an
 // exactly sized heap block, so any access past an end is reported.
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
-#include "../../sds_amd/csrc/sdsj_png.h"
-
-using namespace sdsj;
-
-struct Rd {
-  const uint8_t* p;
-  int operator()(int64_t i) const { return p[i]; }
-};
-
-// The serial sink: what the device's WaveSink does with 64 lanes.
-struct SerialSink {
-  uint8_t* out;
-  int64_t pos;
-  void lit(int b) { out[pos++] = (uint8_t)b; }
-  void match(int dist, int len) {
-    for (int i = 0; i < len; i++) out[pos + i] = out[pos - dist + (i % dist)];
-    pos += len;
-  }
-};
+#include "png_driver_common.h"
 
 static int decode(const uint8_t* buf, int64_t n, PngHdr* h, unsigned long long* hash) {
   Rd rd{buf};
@@ -36,21 +12,7 @@ static int decode(const uint8_t* buf, int64_t n, PngHdr* h, unsigned long long* 
   if (st != SDSJ_OK) return st;
   const int64_t expect = png_raw_bytes(h->width, h->height, h->bpp);
   uint8_t* raw = static_cast<uint8_t*>(malloc((size_t)expect));
-  InfTables* T = new InfTables();
-  PngBits<Rd> br;
-  png_bits_init(br, rd, n, h->idat_pos);
-  SerialSink sink{raw, 0};
-  uint32_t want = 0;
-  st = png_inflate(br, T, sink, expect, &want);
-  delete T;
-  if (st == SDSJ_OK) {
-    uint32_t s1 = 1, s2 = 0;
-    for (int64_t i = 0; i < expect; i++) {
-      s1 = (s1 + raw[i]) % kAdlerMod;
-      s2 = (s2 + s1) % kAdlerMod;
-    }
-    if (((s2 << 16) | s1) != want) st = SDSJ_CORRUPT;
-  }
+  st = inflate_checked(rd, n, h->idat_pos, raw, expect);
   const int64_t pitch = 1 + (int64_t)h->width * h->bpp;
   for (int y = 0; st == SDSJ_OK && y < h->height; y++)
     if (raw[y * pitch] > 4) st = SDSJ_CORRUPT;
@@ -73,9 +35,7 @@ static int decode(const uint8_t* buf, int64_t n, PngHdr* h, unsigned long long* 
       }
       prev.swap(cur);
     }
-    unsigned long long f = 1469598103934665603ull;
-    for (int64_t i = 0; i < (int64_t)w * h->height * 3; i++) f = (f ^ rgb[i]) * 1099511628211ull;
-    *hash = f;
+    *hash = fnv1a64(rgb, (int64_t)w * h->height * 3);
     free(rgb);
   }
   free(raw);
@@ -84,27 +44,10 @@ static int decode(const uint8_t* buf, int64_t n, PngHdr* h, unsigned long long* 
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  std::vector<uint8_t> all;
-  static uint8_t tmp[1 << 16];
-  size_t r;
-  while ((r = fread(tmp, 1, sizeof(tmp), f)) > 0) all.insert(all.end(), tmp, tmp + r);
-  fclose(f);
-  size_t pos = 0;
-  while (pos + 4 <= all.size()) {
-    uint32_t n;
-    memcpy(&n, &all[pos], 4);
-    pos += 4;
-    if (pos + n > all.size()) return 3;
-    uint8_t* buf = static_cast<uint8_t*>(malloc(n ? n : 1));
-    memcpy(buf, &all[pos], n);
-    pos += n;
+  return for_each_record(argv[1], [](const uint8_t* buf, int64_t n) {
     PngHdr h;
     unsigned long long hash = 0;
-    const int st = decode(buf, (int64_t)n, &h, &hash);
+    const int st = decode(buf, n, &h, &hash);
     printf("%d %d %d %llu\n", st, h.width, h.height, hash);
-    free(buf);
-  }
-  return 0;
+  });
 }

@@ -40,7 +40,7 @@ class ImgDescC(ctypes.Structure):
                 ("progressive", i32), ("lat", i32), ("sos_pos", i64), ("off_ptab", i64),
                 ("off_tiles", i64), ("ntiles", i32), ("rs_lay", i32), ("plan_base", i64),
                 ("smooth", i32), ("sm_good", i32), ("sm_bits", ctypes.c_int8 * 60), ("mh", ctypes.c_int8),
-                ("sm_pad", ctypes.c_int8 * 3), ("etab", i32), ("etab_pad", i32),
+                ("sm_pad", ctypes.c_int8 * 3), ("etab", i32), ("png_depth_lace", i32),
                 ("png", i32), ("png_ctype", i32), ("png_bpp", i32), ("png_plte_n", i32),
                 ("png_plte_pos", i64), ("png_idat_pos", i64), ("png_raw", i64), ("off_png", i64)]
 

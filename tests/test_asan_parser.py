@@ -4,39 +4,19 @@ host in sdsj_probe and on the device in k_parse).  Every G1/G5 golden JPEG, trun
 of its headers and with bytes of its headers overwritten, goes through the sanitized parser; the
 build aborts on any out-of-bounds read or undefined behaviour.  Statuses must equal the product
 library's sdsj_probe (same parser, no sanitizer) where it is loadable."""
-import os
 import shutil
-import struct
-import subprocess
-import tempfile
 
 import pytest
 
+from tests import asan_harness as H
 from tests.parser_inputs import inputs as _inputs
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DRIVER = os.path.join(HERE, "asan", "parse_driver.cpp")
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_parser_under_asan_and_ubsan():
-    d = tempfile.mkdtemp()
-    exe = os.path.join(d, "parse_driver")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-I", os.path.join(HERE, "..", "include"), DRIVER, "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = H.build("parse_driver.cpp", "address,undefined", ("-I", H.INCLUDE))
     inputs = _inputs()
-    blob = os.path.join(d, "inputs.bin")
-    with open(blob, "wb") as f:
-        for x in inputs:
-            f.write(struct.pack("<I", len(x)))
-            f.write(x)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, blob], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    rows = [list(map(int, l.split())) for l in r.stdout.splitlines()]
-    assert len(rows) == len(inputs)
+    rows = H.run_records(exe, inputs, H.ASAN_UBSAN)
     assert all(row[0] != 99 for row in rows)
     try:
         from sds_amd import _lib

@@ -5,21 +5,15 @@ stand-alone program (tests/asan/png_ext_driver.cpp, its own main) decodes the ex
 of its small cases, seeded single-byte overwrites and the damaged inputs with a serial decoder built from
 those functions.  It must exit cleanly; every corpus case must decode, and a status of OK is allowed only
 where PIL decodes the same bytes without raising, and then the RGB must equal PIL's."""
-import os
 import shutil
-import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+from tests import asan_harness as H
 from tests import png_ext_synth as E
 from tests import png_synth as S
 from tests.test_asan_png import fnv1a64
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DRIVER = os.path.join(HERE, "asan", "png_ext_driver.cpp")
 
 
 def _inputs():
@@ -43,23 +37,9 @@ def _inputs():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_png_ext_core_under_asan_and_ubsan():
-    d = tempfile.mkdtemp()
-    exe = os.path.join(d, "png_ext_driver")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-I", os.path.join(HERE, "..", "include"), DRIVER, "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = H.build("png_ext_driver.cpp", "address,undefined", ("-I", H.INCLUDE))
     inputs = _inputs()
-    blob = os.path.join(d, "inputs.bin")
-    with open(blob, "wb") as f:
-        for _, x, _ in inputs:
-            f.write(struct.pack("<I", len(x)))
-            f.write(x)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, blob], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    rows = [list(map(int, l.split())) for l in r.stdout.splitlines()]
-    assert len(rows) == len(inputs)
+    rows = H.run_records(exe, [x for _, x, _ in inputs], H.ASAN_UBSAN)
     n_ok = 0
     for (name, data, must), (st, w, h, hsh) in zip(inputs, rows):
         if must:

@@ -4,19 +4,13 @@ every decision of k_parse and k_png_meta.  A stand-alone program (tests/asan/png
 them over the corpus of tests/png_meta_synth.py, the anchors, the truncations of small cases at every byte of their
 chunk regions and the single-byte mutations.  It must exit cleanly; every corpus case must be accepted; a status of
 OK is allowed only where PIL decodes the same bytes; and the library's probe gives the same statuses."""
-import os
 import shutil
-import struct
-import subprocess
-import tempfile
 
 import pytest
 
+from tests import asan_harness as H
 from tests import png_meta_synth as M
 from tests import png_synth as S
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DRIVER = os.path.join(HERE, "asan", "png_meta_driver.cpp")
 
 
 def _inputs():
@@ -37,23 +31,9 @@ def _inputs():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_png_meta_core_under_asan_and_ubsan():
-    d = tempfile.mkdtemp()
-    exe = os.path.join(d, "png_meta_driver")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-I", os.path.join(HERE, "..", "include"), DRIVER, "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = H.build("png_meta_driver.cpp", "address,undefined", ("-I", H.INCLUDE))
     inputs = _inputs()
-    blob = os.path.join(d, "inputs.bin")
-    with open(blob, "wb") as f:
-        for _, x, _ in inputs:
-            f.write(struct.pack("<I", len(x)))
-            f.write(x)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, blob], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    rows = [list(map(int, l.split())) for l in r.stdout.splitlines()]
-    assert len(rows) == len(inputs)
+    rows = H.run_records(exe, [x for _, x, _ in inputs], H.ASAN_UBSAN)
     from sds_amd import _lib as L
     n_ok = 0
     for (name, data, must), (st19, st23, w, h) in zip(inputs, rows):

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 from oracle import oracle as O  # noqa: E402  (checker only)
 from tests import goldens as G  # noqa: E402
 from tests import png_ext_synth as E  # noqa: E402
+from tests import png_gpu as P  # noqa: E402
 from tests import png_synth as S  # noqa: E402
 from tests.test_gpu_frames import _ref  # noqa: E402
 
@@ -42,51 +43,24 @@ def refs():
     return {g: [(n, d, S.pil_rgb(d)) for n, d in c] for g, c in cases.items()}
 
 
-def _by_size(cases):
-    out = {}
-    for n, d, ref in cases:
-        out.setdefault(ref.shape[:2], []).append((n, d, ref))
-    return out
-
-
-def _decode_group_natively(engine, cases):
-    """The group through GpuDecodeBatch(gpu_formats=("jpeg", "png-ext")) at each image's own size (the decode
-    alone): pixels equal PIL's, every sample counted as native PNG, none as a PIL fallback."""
-    from sds_amd.batched import GpuDecodeBatch
-    c0 = engine.counters()
-    total = 0
-    for (h, w), group in _by_size(cases).items():
-        batch = GpuDecodeBatch("png", (h, w), device="cuda", gpu_formats=EXT, on_error="raise")(
-            {"png": [d for _, d, _ in group], "name": [n for n, _, _ in group]})
-        img = batch["image"].cpu().numpy()
-        assert img.shape == (len(group), 3, h, w)
-        for k, (n, _, ref) in enumerate(group):
-            np.testing.assert_array_equal(img[k], ref.transpose(2, 0, 1), err_msg=n)
-        total += len(group)
-    c1 = engine.counters()
-    assert c1["png"] - c0["png"] == total
-    assert c1["fallback"] - c0["fallback"] == 0
-    assert c1["ok"] - c0["ok"] == total
-
-
 def test_adam7_8bit_every_colour_type_and_size(engine, refs):
     assert len(refs["adam7"]) == 5 * len(E.ADAM7_SIZES)
-    _decode_group_natively(engine, refs["adam7"])
+    P.decode_group_natively(engine, refs["adam7"], EXT)
 
 
 def test_depths_1_2_4_gray_and_palette(engine, refs):
     assert len(refs["low"]) == 2 * 3 * len(E.LOW_WIDTHS) * len(E.LOW_HEIGHTS) * 2 + 4
-    _decode_group_natively(engine, refs["low"])
+    P.decode_group_natively(engine, refs["low"], EXT)
 
 
 def test_depth_16(engine, refs):
     assert len(refs["d16"]) == 4 * 3 * 2 * 2
-    _decode_group_natively(engine, refs["d16"])
+    P.decode_group_natively(engine, refs["d16"], EXT)
 
 
 def test_ancillary_chunks_before_the_image_data(engine, refs):
     assert len(refs["chunks"]) == len(E.ANCILLARY) + 1
-    _decode_group_natively(engine, refs["chunks"])
+    P.decode_group_natively(engine, refs["chunks"], EXT)
 
 
 @pytest.mark.parametrize("res,filt,crop", [((24, 40), "bilinear", True), ((150, 90), "bicubic", False)])
@@ -139,7 +113,6 @@ def _mixed_ref(samples, is_png, res, filt, flips, normalize, layout):
 
 @pytest.mark.parametrize("lanes", [1, 4])
 def test_mixed_batch_through_every_entry_point(engine, lanes):
-    from sds_amd.engine import JpegEngine
     res, filt, normalize, layout = (96, 64), "bicubic", True, "hwc"
     samples, is_png = _mixed()
     n = len(samples)
@@ -152,16 +125,7 @@ def test_mixed_batch_through_every_entry_point(engine, lanes):
         outs = {}
         out, st = engine.decode_resize(samples, res, flip=flips, **kw)
         outs["host"] = (out.cpu().numpy(), np.asarray(st))
-        lens = np.array([len(s) for s in samples], np.int32)
-        offs = np.concatenate([[0], np.cumsum((lens.astype(np.int64) + 15) // 16 * 16)[:-1]]).astype(np.int64)
-        blob = np.zeros(int(offs[-1] + lens[-1] + 16), np.uint8)
-        for s, o in zip(samples, offs):
-            blob[o:o + len(s)] = np.frombuffer(s, np.uint8)
-        engine.reserve(JpegEngine.scratch_need(samples, res, filter=filt, normalize=normalize, layout=layout, formats=EXT))
-        out, st = engine.decode_resize_device(torch.from_numpy(blob).cuda(), torch.from_numpy(offs).cuda(),
-                                              torch.from_numpy(lens).cuda(), res,
-                                              flip=torch.tensor(flips, dtype=torch.uint8).cuda(), **kw)
-        outs["device"] = (out.cpu().numpy(), st.cpu().numpy())
+        outs["device"] = P.decode_device(engine, samples, res, flip=flips, **kw)
         tmp = tempfile.mkdtemp()
         paths = []
         for i, s in enumerate(samples):
@@ -173,10 +137,7 @@ def test_mixed_batch_through_every_entry_point(engine, lanes):
         for slot, name in ((0, "submit0"), (1, "files1")):
             out, st = engine.wait(slot)
             outs[name] = (out.cpu().numpy(), np.asarray(st))
-        for name, (o, st) in outs.items():
-            assert (st == 0).all(), (name, st)
-            for k in range(n):
-                np.testing.assert_array_equal(o[k], ref[k], err_msg=f"{name} row {k}")
+        P.assert_rows_equal(outs, ref)
         c1 = engine.counters()
         assert c1["png"] - c0["png"] == len(outs) * sum(is_png)
         assert c1["fallback"] - c0["fallback"] == 0
@@ -228,66 +189,21 @@ def test_need_size_uses_the_probe_under_the_mask(engine):
         f.write(data)
     c0 = engine.counters()
     kw = dict(device="cuda", service=None, resize_kwargs=dict(allow_vertical=True))
-    a = _run(create_standard_image_pipeline("png", (16, 32), gpu_formats=EXT, **kw), {"png": p})["image"]
+    a = P.run_transforms(create_standard_image_pipeline("png", (16, 32), gpu_formats=EXT, **kw), {"png": p})["image"]
     c1 = engine.counters()
-    b = _run(create_standard_image_pipeline("png", (16, 32), **kw), {"png": p})["image"]
+    b = P.run_transforms(create_standard_image_pipeline("png", (16, 32), **kw), {"png": p})["image"]
     assert tuple(a.shape) == tuple(b.shape) and a.shape[0] == 3
     np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy())
     assert c1["png"] - c0["png"] == 1 and c1["fallback"] - c0["fallback"] == 0
 
 
 # -- hand-over and damage ----------------------------------------------------------------------------
-def _run(transforms, sample):
-    for t in transforms:
-        sample = t(sample)
-    return sample
-
-
-def _pipeline_outcome(path, **kw):
-    from sds_amd.presets import create_standard_image_pipeline
-    try:
-        s = _run(create_standard_image_pipeline("png", (16, 20), device="cuda", service=None, **kw), {"png": path})
-        return "ok", s["image"].cpu().contiguous().numpy()
-    except Exception as e:  # noqa: BLE001 -- the exception type is what is compared
-        return "err", type(e)
-
-
 DAMAGE = S.group_damage() + E.group_ext_damage()
 
 
 @pytest.mark.parametrize("name,data", DAMAGE, ids=[n for n, _ in DAMAGE])
 def test_handover_and_damage_equal_the_default_route(engine, name, data):
-    from sds_amd.batched import GpuDecodeBatch
-    p = os.path.join(tempfile.mkdtemp(), "x.png")
-    with open(p, "wb") as f:
-        f.write(data)
-    a, b = _pipeline_outcome(p, gpu_formats=EXT), _pipeline_outcome(p)
-    assert a[0] == b[0], (a, b)
-    if a[0] == "ok":
-        np.testing.assert_array_equal(a[1], b[1])
-    else:
-        assert a[1] is b[1]
-    good = E.make(13, 7, 2, 8, 1, "mixP")[0]
-    outs = []
-    for fm in (EXT, ("jpeg",)):
-        try:
-            r = GpuDecodeBatch("png", (16, 20), device="cuda", gpu_formats=fm, on_error="raise")({"png": [good, data, good]})
-            outs.append(("ok", r["image"].cpu().numpy()))
-        except Exception as e:  # noqa: BLE001
-            outs.append(("err", type(e)))
-    assert outs[0][0] == outs[1][0] == a[0]
-    if outs[0][0] == "ok":
-        np.testing.assert_array_equal(outs[0][1], outs[1][1])
-    else:
-        assert outs[0][1] is outs[1][1]
-    # engine level: status 0 only where PIL decodes the same bytes, and then to the same pixels
-    kind, ref = S.pil_outcome(data)
-    out, st = engine.decode_resize([data], (16, 20), formats=EXT)
-    if kind == "err":
-        assert st[0] != 0
-    if st[0] == 0:
-        assert kind == "ok"
-        np.testing.assert_array_equal(out[0].cpu().numpy(), _ref(ref, (16, 20)))
+    P.check_handover_and_damage(engine, data, EXT, E.make(13, 7, 2, 8, 1, "mixP")[0])
 
 
 def test_damage_split_follows_pil(engine):

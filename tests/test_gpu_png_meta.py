@@ -11,6 +11,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import goldens as G  # noqa: E402
+from tests import png_gpu as P  # noqa: E402
 from tests import png_meta_synth as M  # noqa: E402
 from tests import png_synth as S  # noqa: E402
 
@@ -33,20 +34,6 @@ def files():
     return [(n, d, S.pil_rgb(d)) for n, d in M.meta_files()]
 
 
-def _device(engine, samples, res, formats, **kw):
-    """The device-resident entry point on host bytes: (output, statuses)."""
-    from sds_amd.engine import JpegEngine
-    lens = np.array([len(s) for s in samples], np.int32)
-    offs = np.concatenate([[0], np.cumsum((lens.astype(np.int64) + 15) // 16 * 16)[:-1]]).astype(np.int64)
-    blob = np.zeros(int(offs[-1] + lens[-1] + 16), np.uint8)
-    for s, o in zip(samples, offs):
-        blob[o:o + len(s)] = np.frombuffer(s, np.uint8)
-    engine.reserve(JpegEngine.scratch_need(samples, res, formats=formats, **kw))
-    out, st = engine.decode_resize_device(torch.from_numpy(blob).cuda(), torch.from_numpy(offs).cuda(),
-                                          torch.from_numpy(lens).cuda(), res, formats=formats, **kw)
-    return out.cpu().numpy(), st.cpu().numpy()
-
-
 def _probe(samples, formats):
     from sds_amd import _lib as L
     mask = L.format_mask(formats)
@@ -62,7 +49,7 @@ def test_full_size_decode_equals_pil_on_both_entry_points(engine, files):
         out, st = engine.decode_resize([data], (h, w), layout="hwc", formats=META)
         assert list(st) == [0], name
         np.testing.assert_array_equal(out[0].cpu().numpy(), ref, err_msg=name)
-        out, st = _device(engine, [data], (h, w), META, layout="hwc")
+        out, st = P.decode_device(engine, [data], (h, w), META, layout="hwc")
         assert list(st) == [0], name
         np.testing.assert_array_equal(out[0], ref, err_msg=name)
         runs += 2
@@ -75,7 +62,7 @@ def test_adam7_16_bit_with_metadata_under_the_full_mask(engine):
     ref = S.pil_rgb(data)
     c0 = engine.counters()
     for run in (lambda f: engine.decode_resize([data], (7, 13), layout="hwc", formats=f),
-                lambda f: _device(engine, [data], (7, 13), f, layout="hwc")):
+                lambda f: P.decode_device(engine, [data], (7, 13), f, layout="hwc")):
         out, st = run(FULL)
         assert list(np.asarray(st)) == [0]
         np.testing.assert_array_equal(np.asarray(out[0].cpu() if hasattr(out[0], "cpu") else out[0]), ref)
@@ -108,7 +95,7 @@ def test_mixed_batch_statuses_counter_and_mask_off(engine, files):
     res = (32, 32)
     c0 = engine.counters()
     out_h, st_h = engine.decode_resize(samples, res, formats=META)
-    out_d, st_d = _device(engine, samples, res, META)
+    out_d, st_d = P.decode_device(engine, samples, res, META)
     c1 = engine.counters()
     np.testing.assert_array_equal(np.asarray(st_h), want)
     np.testing.assert_array_equal(st_d, want)
@@ -117,7 +104,7 @@ def test_mixed_batch_statuses_counter_and_mask_off(engine, files):
     assert c1["unsupported"] - c0["unsupported"] == 2 * len(refused)
     # the bit off: the plain files still decode, to the same pixels; nothing with metadata does
     for fm in (EXT, ("jpeg", "png")):
-        out_o, st_o = _device(engine, samples, res, fm)
+        out_o, st_o = P.decode_device(engine, samples, res, fm)
         assert (st_o[(kinds == "meta") | (kinds == "refused")] == -2).all(), fm
         assert (st_o[(kinds == "plain") | (kinds == "jpeg")] == 0).all(), fm
         keep = st_o == 0
@@ -132,10 +119,10 @@ def test_mask_off(engine, files):
     c0 = engine.counters()
     _, st = engine.decode_resize(batch, (16, 16), formats=EXT)
     assert (np.asarray(st) == -2).all(), st
-    _, st = _device(engine, batch, (16, 16), EXT)
+    _, st = P.decode_device(engine, batch, (16, 16), EXT)
     assert (st == -2).all(), st
     assert engine.counters()["png"] == c0["png"]
-    _, st = _device(engine, late, (16, 16), FULL)
+    _, st = P.decode_device(engine, late, (16, 16), FULL)
     assert (st == 0).all(), st
 
 
