@@ -167,7 +167,7 @@ struct ImgDesc {
   int64_t off_seg;      // int32 [nseg + 2]: segment start bytes, then the stream length
   int64_t off_sub;      // SubState [nsub_cap]
   int64_t off_rec;      // SyncRec [nsub_cap][kRec]
-  int64_t off_coef;     // int16 [total_blocks * 64], zigzag order within a block
+  int64_t off_coef;     // coefficient blocks in decode order (coef_bytes: compact or int16 format)
   int64_t off_planes;
   int64_t off_rgb;      // uint8 RGB rows [src_y0, src_y1) x [src_x0, src_x0 + src_w)
   int64_t off_tmp;      // uint8 horizontal-pass output (yl - yf) x out_w x 3
@@ -346,6 +346,50 @@ SDSJ_HD inline int gen_route(int kt) {
 
 SDSJ_HD inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 SDSJ_HD inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// Distinct Huffman table slots the scan uses (DC keys td, AC keys 4 | ta), counted as load_tables
+// counts them: more than 4 selects the 10-bit entropy route (kRtEnt10, image_routes).
+SDSJ_HD inline int huff_slots(const ImgDesc& d) {
+  int keys[2 * kMaxComp], ns = 0;
+  for (int c = 0; c < d.ncomp; c++)
+    for (int k = 0; k < 2; k++) {
+      const int key = k ? (4 | d.comp[c].ta) : d.comp[c].td;
+      bool seen = false;
+      for (int q = 0; q < ns; q++) seen |= keys[q] == key;
+      if (!seen) keys[ns++] = key;
+    }
+  return ns;
+}
+
+// Coefficient blocks between the entropy decoder and k_idct, at off_coef in decode order (N = total_blocks).
+// Progressive images (k_prog) and the 10-bit entropy route (k_entwrite<10>): 128-byte blocks, 64 int16 in
+// zigzag order; latency-mode images keep them too.  Other baseline images of the 11-bit routes (coef_compact;
+// k_entwrite<11, .., true>) halve that, in three
+// sub-regions, each 256-byte aligned:
+//   main  64 N bytes  bytes 0-1 = flag | 11 bits of DC << 1 | 4 bits of AC 63 << 12 (both signed), byte k + 1 = the
+//                     low 8 bits of AC k (zigzag 1..62)
+//   dc     2 N bytes  flagged blocks only: the block's DC as int16 (the 16-bit wrap of the predictor sum)
+//   hi    64 N bytes  flagged blocks only: byte k = what AC k (1..62) holds beyond its sign-extended low byte, in
+//                     units of 256; bytes 0 (low) and 63 = what AC 63 holds beyond its 4 bits, in units of 16
+// A block is flagged when the main slot cannot hold it: an AC symbol of more than 7 bits, an AC 63 of more than
+// 3, or a DC outside 11 bits (what an 8-bit baseline encoder can produce fits).  Its other hi bytes are zeros;
+// the dc and hi entries of other blocks are never touched (no traffic) and never read.  AC k = sext8(low byte),
+// plus (sext8(hi[k]) << 8) wrapped to 16 bits in a flagged block, so the full 16-bit range is kept.  (The DC
+// sits inside the main slot because a 2-byte store per block to a side region cost the write pass 4 ms per
+// 65,536 VGA images: every lane of such a store touches another cache line.)
+constexpr int kCoefFull = 128, kCoefMain = 64;
+// (slots: huff_slots(d), for a caller that has it already)
+// Latency-mode images (ImgDesc::lat) keep int16 blocks too: on their few workgroups per image the compact write
+// pass measured 10.6 us slower per one-image call (96.3 -> 106.9 us), and the bytes saved do not matter there.
+SDSJ_HD inline bool coef_compact(const ImgDesc& d, int slots) {
+  return !d.progressive && !d.png && !d.lat && slots <= 4;
+}
+SDSJ_HD inline bool coef_compact(const ImgDesc& d) { return coef_compact(d, huff_slots(d)); }
+SDSJ_HD inline int64_t coef_dc_off(int64_t blocks) { return align_up(blocks * kCoefMain, 256); }
+SDSJ_HD inline int64_t coef_hi_off(int64_t blocks) { return coef_dc_off(blocks) + align_up(blocks * 2, 256); }
+SDSJ_HD inline int64_t coef_bytes(const ImgDesc& d, int slots) {
+  return coef_compact(d, slots) ? coef_hi_off(d.total_blocks) + d.total_blocks * kCoefMain : d.total_blocks * kCoefFull;
+}
 
 // jutils.c jpeg_natural_order (+16 guard entries)
 #if defined(__HIPCC__)

@@ -241,7 +241,7 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   mark(5);
   SDSJ_HIP(e, launch_entsync(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint));
   mark(6);
-  SDSJ_HIP(e, launch_entwrite(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint));
+  SDSJ_HIP(e, launch_entwrite(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint, small));
   mark(7);
   SDSJ_HIP(e, launch_idct(n, ln.descs, ln.tables, e->scratch.get(), s));
   mark(8);

@@ -44,7 +44,7 @@ constexpr bool kStats = SDSJ_STATS != 0;
 
 constexpr int kEntThreads = kDecodeThreads;
 constexpr int kLutEntries = 1 << 13;  // LDS lookup capacity: 4 tables x 2^11 or 8 x 2^10
-constexpr int kStageStride = 64;      // int16 per lane staging block (one 128-byte block)
+constexpr int kStageStride = 64;      // int16 per lane staging block (one 128-byte block; compact format: kStageCompact)
 template <int NT>
 constexpr int max_tasks() { return 4 * NT; }  // sync tasks per round (more: picked up by the next round)
 // k_entsync is latency-bound (a few serial re-decodes per image): one wave per image keeps more
@@ -1270,11 +1270,41 @@ __device__ __forceinline__ void store_coef16(void* p, uint4 v) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   __builtin_nontemporal_store(v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u*>(p));
 }
-template <class TT>
+// The compact format's rare paths (sdsj_common.h coef_compact), out of line: they cost the decode loop a
+// compare each and no registers.  (One lane's stores to the same bytes stay in program order.)
+__device__ __forceinline__ void zero_hi_slot(uint8_t* hslot) {
+  uint4* z = reinterpret_cast<uint4*>(hslot);
+#pragma unroll
+  for (int i = 0; i < 4; i++) z[i] = make_uint4(0, 0, 0, 0);
+}
+// An AC value of more than 7 bits, or an AC 63 of more than 3, at zigzag position wpos of the lane's current
+// block (`first`: the block's first such value zeroes its hi slot): the byte that, shifted by 8 and added to
+// the sign-extended low byte, gives the value.  AC 63 has only 4 bits in the main slot: what it holds beyond
+// them, in units of 16, goes to hi[0] (low byte) and hi[63].
+__device__ __attribute__((noinline)) void store_wide(uint8_t* hslot, int wpos, int val, bool first) {
+  if (first) zero_hi_slot(hslot);
+  if (wpos == 63) {
+    const int rem = (val - ((val << 28) >> 28)) >> 4;
+    hslot[0] = (uint8_t)rem;
+    hslot[63] = (uint8_t)((rem - (int)(int8_t)rem) >> 8);
+  } else {
+    hslot[wpos] = (uint8_t)((val - (int)(int8_t)val) >> 8);
+  }
+}
+// The end of a flagged block (one with a hi slot, or whose DC leaves 11 bits): its DC in full.
+__device__ __attribute__((noinline)) void store_flagged_dc(uint8_t* hslot, int16_t* dcp, int16_t dc, bool first) {
+  if (first) zero_hi_slot(hslot);
+  *dcp = dc;
+}
+// The write pass's LDS.  ST: the stage's coefficient type, STRIDE: coefficients per lane -- int8_t x 80 for
+// the compact format (the 64-byte main slot, then a spare byte where AC 63 and the EOB's zero land), else
+// int16_t x 64
+constexpr int kStageCompact = 80;
+template <class TT, class ST, int STRIDE>
 struct LdsWriteT {
   unsigned long long t0, it;
   TT T;
-  alignas(16) int16_t stage[kEntThreads * kStageStride];
+  alignas(16) ST stage[kEntThreads * STRIDE];
   uint32_t flist[kEntThreads / 64][64];  // (thread << 24) | block index (total_blocks < 2^24)
   int32_t bad;
   unsigned long long sym;
@@ -1336,21 +1366,28 @@ __device__ int load_write_tables(WriteTables& W, const EntTables* g, int32_t* tm
   return ns;
 }
 
-template <int LB>
+// CP: the variant that writes the compact coefficient format (sdsj_common.h coef_compact: LB = 11 images
+// outside latency mode); each variant skips the other's images.  A lane's images are all in latency mode or
+// none is (k_parse's `small`), so launch_entwrite launches one of the two.
+template <int LB, bool CP>
 __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
                                uint8_t* __restrict__ scratch) {
+  static_assert(!CP || LB == 11, "the compact format belongs to the 11-bit routes");
   ImgDesc* d = &descs[img];
   if (d->status != SDSJ_OK) return;
   using TT = std::conditional_t<LB == 11, WriteTables, LutTables>;
-  __shared__ LdsWriteT<TT> L;
+  constexpr bool kCompact = CP;
+  using ST = std::conditional_t<kCompact, int8_t, int16_t>;
+  constexpr int kStride = kCompact ? kStageCompact : kStageStride;
+  __shared__ LdsWriteT<TT, ST, kStride> L;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   int ns;
   if constexpr (LB == 11) ns = load_write_tables(L.T, &tables[d->etab], reinterpret_cast<int32_t*>(L.stage));
   else ns = load_tables<LB>(L.T, &tables[d->etab]);
-  if (!variant_owns<LB>(ns)) return;
+  if (!variant_owns<LB>(ns) || coef_compact(*d) != kCompact) return;
   {
     uint4* z4 = reinterpret_cast<uint4*>(L.stage);
-    for (int i = t; i < kEntThreads * kStageStride * 2 / 16; i += kEntThreads) z4[i] = make_uint4(0, 0, 0, 0);
+    for (int i = t; i < kEntThreads * kStride * (int)sizeof(ST) / 16; i += kEntThreads) z4[i] = make_uint4(0, 0, 0, 0);
   }
   if (t == 0) {
     L.bad = 0;
@@ -1364,11 +1401,13 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
   const uint32_t* src = reinterpret_cast<const uint32_t*>(scratch + d->off_ustream);
   const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
   const SubState* sub = reinterpret_cast<const SubState*>(scratch + d->off_sub);
-  int16_t* coef = reinterpret_cast<int16_t*>(scratch + d->off_coef);
+  uint8_t* coef = scratch + d->off_coef;  // 128-byte blocks, or the compact format's main slots
+  int16_t* cdc = reinterpret_cast<int16_t*>(coef + coef_dc_off(d->total_blocks));  // (compact) flagged blocks' DC
+  uint8_t* chi = coef + coef_hi_off(d->total_blocks);                              // (compact) hi slots
   const int nsub = d->nsub;
   const int blocks_per_seg = d->restart_interval ? d->restart_interval * K.bpm : (int)d->total_blocks;
   const int ncomp = d->ncomp;
-  const int my_base = t * kStageStride;
+  const int my_base = t * kStride;
   int bad = 0;
   unsigned long long nsym = 0, witers = 0;
 
@@ -1442,6 +1481,8 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
     // bookkeeping (predictors, MCU position and context, block index, stop rule) runs there too, once
     // per flush instead of as selects on every step.
     bool pending = false;
+    bool wide = false;  // (compact) the current block has a hi slot
+    int lastv = 0;      // (compact) the last value this lane decoded
     while (__builtin_amdgcn_ballot_w64(run)) {
       if (run) bits_fill(b);
       for (;;) {
@@ -1463,9 +1504,25 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
             // every symbol stores
             pc += isdc ? val : 0;
             const int zn = z + adv, wpos = zn < 64 ? zn - 1 : 63;
-            L.stage[my_base + wpos] = (int16_t)(isdc ? pc : val);
             // block end by selects (no branches): the component's predictor back, the next block's out
             done = zn > 63;
+            // compact format: AC k's low byte at byte k + 1 (the DC symbol's lands in byte 1, which the block
+            // end overwrites with the DC; position 63 in the spare byte).  One compare sends what the main slot
+            // cannot hold -- more than 7 bits, or more than 3 at position 63 -- to the hi slot (rare; a DC symbol
+            // of more than 7 bits passes the compare and does nothing).  lastv: a completed block's last
+            // value, AC 63 (0 after an EOB), whose 4 low bits the block end packs next to the DC
+            if constexpr (kCompact) {
+              L.stage[my_base + wpos + 1] = (ST)val;
+              lastv = val;
+              if (__builtin_expect((done ? s + 4 : s) > 7, 0)) {
+                if (!isdc) {
+                  store_wide(chi + (int64_t)g * kCoefMain, wpos, val, !wide);
+                  wide = true;
+                }
+              }
+            } else {
+              L.stage[my_base + wpos] = (ST)(isdc ? pc : val);
+            }
             z = done ? 0 : zn;
           } else {
             int s, r, sb = 0;
@@ -1474,18 +1531,29 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
             bad |= sb;
             pc += isdc ? val : 0;
             const int zp = z + r, wpos = zp < 63 ? zp : 63;
-            L.stage[my_base + wpos] = (int16_t)(isdc ? pc : val);
+            L.stage[my_base + wpos] = (ST)(isdc ? pc : val);
             done = next_z(z, s, r);
           }
           pending = done;
         }
-        // cooperative flush of the blocks completed since the last flush: 8 lanes x 16 B per block
+        // cooperative flush of the blocks completed since the last flush: 16 B per lane, 8 lanes per 128-byte
+        // block or 4 per compact 64-byte slot
         const uint64_t m = u % kFlushEvery == kFlushEvery - 1 ? __builtin_amdgcn_ballot_w64(pending) : 0ull;
         if (m) {
           const int cnt = __popcll(m);
           if (pending) {
             const int idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
             L.flist[wv][idx] = ((uint32_t)t << 24) | (uint32_t)g;
+            if constexpr (kCompact) {
+              // bytes 0-1 of the main slot: flag | 11 bits of DC << 1 | 4 bits of AC 63 << 12; a DC outside 11
+              // bits flags the block too, and a flagged block's DC goes to the dc region in full
+              const int16_t dc16 = (int16_t)pc;
+              const bool flag = wide | ((uint32_t)((int)dc16 + 1024) >= 2048u);
+              if (__builtin_expect(flag, 0)) store_flagged_dc(chi + (int64_t)g * kCoefMain, cdc + g, dc16, !wide);
+              *reinterpret_cast<uint16_t*>(&L.stage[my_base]) =
+                  (uint16_t)((flag ? 1u : 0u) | (((uint32_t)pc & 0x7FFu) << 1) | (((uint32_t)lastv & 15u) << 12));
+              wide = false;
+            }
             // the block end: the component's predictor back, the next block's out
             if constexpr (LB == 11) {
               // (pc, p0, p1) -> (p0, p1, pc) with 3 components in the scan, (pc, p0) -> (p0, pc) with 2
@@ -1514,13 +1582,15 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
           // (a wave's LDS accesses execute in issue order: the reads below see these writes, and the
           // owner's next stage writes land after the clears -- no waits beyond the data dependences)
           __builtin_amdgcn_wave_barrier();
-          for (int b0 = 0; b0 < cnt; b0 += 8) {
-            const int bi = b0 + (lane >> 3);
+          // (a block is kPer lanes x 16 B: 8 blocks per wave instruction, 16 in the compact format)
+          constexpr int kPer = kCompact ? kCoefMain / 16 : kCoefFull / 16;
+          for (int b0 = 0; b0 < cnt; b0 += 64 / kPer) {
+            const int bi = b0 + lane / kPer;
             if (bi < cnt) {
               const uint32_t f = L.flist[wv][bi];
-              uint4* sp = reinterpret_cast<uint4*>(L.stage + (f >> 24) * kStageStride) + (lane & 7);
+              uint4* sp = reinterpret_cast<uint4*>(L.stage + (f >> 24) * kStride) + (lane % kPer);
               const uint4 v = *sp;
-              store_coef16(reinterpret_cast<uint4*>(coef + (int64_t)(f & 0xFFFFFF) * 64) + (lane & 7), v);
+              store_coef16(reinterpret_cast<uint4*>(coef + (int64_t)(f & 0xFFFFFF) * (kPer * 16)) + (lane % kPer), v);
               *sp = make_uint4(0, 0, 0, 0);
             }
           }
@@ -1552,11 +1622,11 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
 }
 
 
-template <int LB, int PHASE, int NTS = kSyncThreads, int NSPEC = kEntThreads>
+template <int LB, int PHASE, int NTS = kSyncThreads, int NSPEC = kEntThreads, bool CP = false>
 __device__ __forceinline__ void ent_phase(int img, int grp, ImgDesc* descs, const EntTables* tables, uint8_t* scratch) {
   if (PHASE == 0) entspec_image<LB, NSPEC>(img, grp, descs, tables, scratch);
   else if (PHASE == 1) entsync_image<LB, NTS>(img, descs, tables, scratch);
-  else entwrite_image<LB>(img, grp, descs, tables, scratch);
+  else entwrite_image<LB, CP>(img, grp, descs, tables, scratch);
 }
 
 // The entropy kernels take images from a route list.  MODE 0: one workgroup per list entry (grid =
@@ -1564,7 +1634,7 @@ __device__ __forceinline__ void ent_phase(int img, int grp, ImgDesc* descs, cons
 // MODE 1: a small grid strides over the list and runs each image's groups in turn (LB = 10).  MODE 3:
 // (image, group) tasks of the LB = 11 images with ent_groups > 1, a grid of at most kTaskGrid
 // workgroups striding over them.  The sync pass is per image (MODE 0 for them too).
-template <int LB, int PHASE, int RT, int MODE, int NTS = kSyncThreads, int NSPEC = kEntThreads>
+template <int LB, int PHASE, int RT, int MODE, int NTS = kSyncThreads, int NSPEC = kEntThreads, bool CP = false>
 __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables, uint8_t* scratch, int32_t* routes,
                                          int cap) {
   if (MODE == 3) {  // (image, group) tasks (k_plan's group_tasks list); a capped grid strides over them
@@ -1572,7 +1642,7 @@ __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables
     const int32_t* tasks = group_tasks(routes, cap);
     for (int k = blockIdx.x; k < nt; k += gridDim.x) {
       const int task = tasks[k];
-      ent_phase<LB, PHASE, NTS, NSPEC>(task >> kGroupShift, task & ((1 << kGroupShift) - 1), descs, tables, scratch);
+      ent_phase<LB, PHASE, NTS, NSPEC, CP>(task >> kGroupShift, task & ((1 << kGroupShift) - 1), descs, tables, scratch);
       __syncthreads();  // LDS reuse by the next task
     }
     return;
@@ -1581,7 +1651,7 @@ __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables
   const int32_t* list = route_list(routes, cap, RT);
   if (MODE == 0) {  // one entry per workgroup at the full grid; a cold route's small grid strides (route_grid)
     for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
-      ent_phase<LB, PHASE, NTS, NSPEC>(list[li], 0, descs, tables, scratch);
+      ent_phase<LB, PHASE, NTS, NSPEC, CP>(list[li], 0, descs, tables, scratch);
       __syncthreads();  // LDS reuse by the next entry
     }
     return;
@@ -1590,10 +1660,10 @@ __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables
     const int img = list[li];
     const int G = PHASE == 1 ? 1 : descs[img].ent_groups;
     if (MODE == 2) {
-      if ((int)blockIdx.y < G) ent_phase<LB, PHASE, NTS, NSPEC>(img, blockIdx.y, descs, tables, scratch);
+      if ((int)blockIdx.y < G) ent_phase<LB, PHASE, NTS, NSPEC, CP>(img, blockIdx.y, descs, tables, scratch);
     } else {
       for (int grp = 0; grp < G; grp++) {
-        ent_phase<LB, PHASE, NTS, NSPEC>(img, grp, descs, tables, scratch);
+        ent_phase<LB, PHASE, NTS, NSPEC, CP>(img, grp, descs, tables, scratch);
         __syncthreads();  // LDS reuse by the next group
       }
     }
@@ -1628,11 +1698,11 @@ __global__ void __launch_bounds__(NTS) k_entsync(ImgDesc* __restrict__ descs, co
   ent_feed<LB, 1, RT, MODE, NTS>(descs, tables, scratch, routes, cap);
 }
 
-template <int LB, int RT, int MODE>
+template <int LB, int RT, int MODE, bool CP>
 __global__ void __launch_bounds__(kEntThreads) k_entwrite(ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
                                                           uint8_t* __restrict__ scratch, int32_t* __restrict__ routes,
                                                           int cap) {
-  ent_feed<LB, 2, RT, MODE>(descs, tables, scratch, routes, cap);
+  ent_feed<LB, 2, RT, MODE, kSyncThreads, kEntThreads, CP>(descs, tables, scratch, routes, cap);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1852,18 +1922,23 @@ hipError_t launch_entsync(int n, ImgDesc* descs, void* etab, uint8_t* scratch, i
 }
 
 hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scratch, int32_t* routes, int cap,
-                           hipStream_t s, uint64_t rm, uint64_t hint) {
+                           hipStream_t s, uint64_t rm, uint64_t hint, bool small) {
   const int g = n;  // one workgroup per image on the main route
   const EntTables* tables = static_cast<const EntTables*>(etab);
   const int gs = g < 256 ? g : 256;
-  if (route_on(rm, kRtEnt11))
-    hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0>), dim3(route_grid(hint, kRtEnt11, g)), dim3(kEntThreads), 0, s, descs,
-                       tables, scratch, routes, cap);
-  if (route_on(rm, kRtEnt11M))
-    hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3>), dim3(route_grid(hint, kRtEnt11M, task_grid(n))), dim3(kEntThreads), 0,
-                       s, descs, tables, scratch, routes, cap);
+  // (latency-mode lanes keep the int16 coefficient format: coef_compact)
+  if (route_on(rm, kRtEnt11)) {
+    const dim3 grid(route_grid(hint, kRtEnt11, g));
+    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
+    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
+  }
+  if (route_on(rm, kRtEnt11M)) {
+    const dim3 grid(route_grid(hint, kRtEnt11M, task_grid(n)));
+    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
+    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
+  }
   if (route_on(rm, kRtEnt10))
-    hipLaunchKernelGGL((k_entwrite<10, kRtEnt10, 1>), dim3(route_grid(hint, kRtEnt10, gs)), dim3(kEntThreads), 0, s, descs,
+    hipLaunchKernelGGL((k_entwrite<10, kRtEnt10, 1, false>), dim3(route_grid(hint, kRtEnt10, gs)), dim3(kEntThreads), 0, s, descs,
                        tables, scratch, routes, cap);
   return hipGetLastError();
 }

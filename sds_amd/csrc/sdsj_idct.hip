@@ -32,6 +32,49 @@ constexpr int kIdctGrid = SDSJ_IDCT_GRID;  // workgroups per image (each strides
 // workgroups would land on the same XCDs; 17 rotates them by one XCD per image)
 constexpr int kIdctGridMax = 17;
 
+// The compact coefficient format's side of k_idct (sdsj_common.h coef_compact).  m: a block's 64-byte main slot
+// as 16 dwords (bytes 0-1 flag | DC << 1 | AC 63 << 12, byte k + 1 = the low byte of AC k, k = 1..62); h: a
+// flagged block's hi slot (byte k = AC k's part beyond its low byte; AC 63's beyond its 4 bits: bytes 0 and 63).
+// Any AC byte outside row 0 (zigzag positions 0, 1, 5, 6, 14, 15, 27, 28) -- a coefficient is zero iff both its
+// bytes are.
+__device__ __forceinline__ uint32_t coef8_ac_main(const uint32_t* m) {
+  uint32_t ac = (m[0] & 0xFF00F000u) | (m[1] & 0x0000FFFFu) | m[2] | (m[3] & 0x00FFFFFFu) | (m[4] & 0xFFFFFF00u) |
+                m[5] | m[6] | (m[7] & 0xFFFF0000u);
+#pragma unroll
+  for (int i = 8; i < 16; i++) ac |= m[i];
+  return ac;
+}
+__device__ __forceinline__ uint32_t coef8_ac_hi(const uint32_t* h) {
+  uint32_t ac = (h[0] & 0xFFFF00FFu) | (h[1] & 0xFF0000FFu) | h[2] | (h[3] & 0x0000FFFFu) | h[4] | h[5] |
+                (h[6] & 0x00FFFFFFu) | (h[7] & 0xFFFFFF00u);
+#pragma unroll
+  for (int i = 8; i < 16; i++) ac |= h[i];
+  return ac;
+}
+// Dequantisation straight from the byte extracts: AC k = sext8(main byte k + 1), plus (sext8(hi byte k) << 8)
+// wrapped to 16 bits for a flagged block (WIDE); AC 63 = its 4 bits of the first word, plus 16 x (hi bytes 0
+// and 63 as an int16) when flagged.  DC = dcv.  q: the component's table in zigzag order (LDS).
+template <bool WIDE>
+__device__ __forceinline__ void dequant8(const uint32_t* m, const uint32_t* h, const int32_t* q, int dcv, int* x) {
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const int4 qv = *reinterpret_cast<const int4*>(&q[i * 4]);
+    const int qq[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int k = i * 4 + j;
+      int cv;
+      if (k == 0) cv = dcv;
+      else if (k == 63) cv = __builtin_amdgcn_sbfe((int)m[0], 12, 4);
+      else cv = __builtin_amdgcn_sbfe((int)m[(k + 1) >> 2], 8 * ((k + 1) & 3), 8);
+      if (WIDE && k == 63)
+        cv = (int)(int16_t)(cv + ((__builtin_amdgcn_sbfe((int)h[0], 0, 8) + (__builtin_amdgcn_sbfe((int)h[15], 24, 8) << 8)) << 4));
+      else if (WIDE && k > 0) cv = (int)(int16_t)(cv + (__builtin_amdgcn_sbfe((int)h[i], 8 * j, 8) << 8));
+      x[natural_order(k)] = wrap16(cv * qq[j]);
+    }
+  }
+}
+
 // Work unit = a group: 8 horizontally adjacent blocks of one component, one per thread, so each of
 // a block's 8 row stores joins the group's other 7 in 64 contiguous bytes of a plane row.  The
 // block stays in registers through both passes (64 values), so there is no LDS transpose.
@@ -91,7 +134,15 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
   }
   __syncthreads();
   const int lb = t & 7;  // this lane's block within its group
-  const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + d->off_coef);
+  // coefficient blocks (sdsj_common.h coef_compact): 64-byte main slots with the dc and hi sub-regions, or
+  // 128-byte int16 blocks
+  // (evaluated by every wave, on its scalar unit from the descriptor: the value stays in an SGPR and the format
+  // branch below stays uniform.  Held in LDS instead, once per workgroup, the branch became a vector one and
+  // k_idct went 15.6 -> 24.4 ms per 65,536)
+  const bool compact = coef_compact(*d);
+  const uint8_t* coef = scratch + d->off_coef;
+  const int16_t* cdc = reinterpret_cast<const int16_t*>(coef + coef_dc_off(d->total_blocks));
+  const uint8_t* chi = coef + coef_hi_off(d->total_blocks);
   uint8_t* planes = scratch + d->off_planes;
   const int ngroups = gstart[ncomp];
   // blocks the entropy decoder left zero (jdhuff.c insufficient_data): from vend[k] to the end of
@@ -135,30 +186,57 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
     int c, by, bx, g;
     locate(grp, c, by, bx, g);
     if (g < 0) continue;
-    // the block (zigzag order, k_entwrite / k_prog), or zeros where the entropy decoder left it zero
-    const uint4* src = reinterpret_cast<const uint4*>(coef + (int64_t)g * 64);
+    // the block (zigzag order), or zeros where the entropy decoder left it zero, dequantised as vpmullw does:
+    // the low 16 bits of coef * quantval, zigzag position k into row-major natural_order(k).  `ac`: any raw
+    // coefficient outside row 0 (the SIMD pass 1's zero test)
     const bool zb = zero_block(g);
-    uint4 raw[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) raw[i] = zb ? make_uint4(0, 0, 0, 0) : src[i];
-    // `ac`: any raw coefficient outside row 0 (the SIMD pass 1's zero test); row 0 is zigzag positions
-    // 0, 1, 5, 6, 14, 15, 27 and 28
-    uint32_t ac = raw[0].y | (raw[0].z & 0xFFFFu) | (raw[0].w & 0xFFFF0000u) | raw[1].x | raw[1].y | raw[1].z |
-                  raw[3].x | (raw[3].y & 0xFFFFu) | (raw[3].z & 0xFFFF0000u) | raw[3].w;
-#pragma unroll
-    for (int i = 2; i < 8; i++) ac |= i == 3 ? 0u : (raw[i].x | raw[i].y | raw[i].z | raw[i].w);
-    // DEQUANTIZE as vpmullw: the low 16 bits of coef * quantval, zigzag position k into row-major
-    // natural_order(k)
     int x[64];
+    uint32_t ac;
+    if (compact) {
+      // k_entwrite<11>'s 64-byte main slot; a flagged block's DC and hi slot too (rare, divergent)
+      const uint4* src = reinterpret_cast<const uint4*>(coef + (int64_t)g * kCoefMain);
+      uint32_t m[16];
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int4 q0 = *reinterpret_cast<const int4*>(&qt[c][i * 8]), q1 = *reinterpret_cast<const int4*>(&qt[c][i * 8 + 4]);
-      const uint32_t w[4] = {raw[i].x, raw[i].y, raw[i].z, raw[i].w};
-      const int q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+      for (int i = 0; i < 4; i++) {
+        const uint4 v = zb ? make_uint4(0, 0, 0, 0) : src[i];
+        m[4 * i] = v.x, m[4 * i + 1] = v.y, m[4 * i + 2] = v.z, m[4 * i + 3] = v.w;
+      }
+      ac = coef8_ac_main(m);
+      if (m[0] & 1u) {
+        const int dcv = cdc[g];
+        const uint4* hs = reinterpret_cast<const uint4*>(chi + (int64_t)g * kCoefMain);
+        uint32_t h[16];
 #pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const int cv = (int)(int16_t)((w[k >> 1] >> ((k & 1) * 16)) & 0xFFFF);
-        x[natural_order(i * 8 + k)] = wrap16(cv * q[k]);
+        for (int i = 0; i < 4; i++) {
+          const uint4 v = hs[i];
+          h[4 * i] = v.x, h[4 * i + 1] = v.y, h[4 * i + 2] = v.z, h[4 * i + 3] = v.w;
+        }
+        ac |= coef8_ac_hi(h);
+        dequant8<true>(m, h, qt[c], dcv, x);
+      } else {
+        dequant8<false>(m, m, qt[c], __builtin_amdgcn_sbfe((int)m[0], 1, 11), x);
+      }
+    } else {
+      // 128-byte int16 blocks (k_entwrite<10> / k_prog)
+      const uint4* src = reinterpret_cast<const uint4*>(coef + (int64_t)g * kCoefFull);
+      uint4 raw[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) raw[i] = zb ? make_uint4(0, 0, 0, 0) : src[i];
+      // row 0 is zigzag positions 0, 1, 5, 6, 14, 15, 27 and 28
+      ac = raw[0].y | (raw[0].z & 0xFFFFu) | (raw[0].w & 0xFFFF0000u) | raw[1].x | raw[1].y | raw[1].z |
+           raw[3].x | (raw[3].y & 0xFFFFu) | (raw[3].z & 0xFFFF0000u) | raw[3].w;
+#pragma unroll
+      for (int i = 2; i < 8; i++) ac |= i == 3 ? 0u : (raw[i].x | raw[i].y | raw[i].z | raw[i].w);
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const int4 q0 = *reinterpret_cast<const int4*>(&qt[c][i * 8]), q1 = *reinterpret_cast<const int4*>(&qt[c][i * 8 + 4]);
+        const uint32_t w[4] = {raw[i].x, raw[i].y, raw[i].z, raw[i].w};
+        const int q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          const int cv = (int)(int16_t)((w[k >> 1] >> ((k & 1) * 16)) & 0xFFFF);
+          x[natural_order(i * 8 + k)] = wrap16(cv * q[k]);
+        }
       }
     }
     // pass 1: columns.  A block whose rows 1..7 are all zero takes the SIMD shortcut (vpsllw: every

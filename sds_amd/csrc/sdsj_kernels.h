@@ -68,8 +68,9 @@ hipError_t launch_entspec(int n, ImgDesc* descs, const ImgTables* specs, void* e
 // k_entsync (sync rounds + segmented scan)
 hipError_t launch_entsync(int n, ImgDesc* descs, void* etab, uint8_t* scratch, int32_t* routes, int cap, hipStream_t s,
                           uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
+// (small: as for launch_entspec -- the lane's images are in latency mode and keep int16 coefficient blocks)
 hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scratch, int32_t* routes, int cap,
-                           hipStream_t s, uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
+                           hipStream_t s, uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes, bool small = false);
 hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s);
 hipError_t launch_color(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                         uint64_t rm = kAllRoutes);

@@ -39,20 +39,6 @@ SDSJ_HD inline int warm_for(int sub_bits, int floor_bits) {
   return sub_bits * 3 / 2 < w ? sub_bits * 3 / 2 : w;
 }
 
-// Distinct Huffman table slots the scan uses (DC keys td, AC keys 4 | ta), counted as load_tables
-// counts them: more than 4 selects the 10-bit entropy route (kRtEnt10, image_routes).
-SDSJ_HD inline int huff_slots(const ImgDesc& d) {
-  int keys[2 * kMaxComp], ns = 0;
-  for (int c = 0; c < d.ncomp; c++)
-    for (int k = 0; k < 2; k++) {
-      const int key = k ? (4 | d.comp[c].ta) : d.comp[c].td;
-      bool seen = false;
-      for (int q = 0; q < ns; q++) seen |= keys[q] == key;
-      if (!seen) keys[ns++] = key;
-    }
-  return ns;
-}
-
 // frames = true: raw RGB frames (sdsj_resize_frames_device): the unfused passes read the frame rows
 // in place (off_rgb / rgb_pitch are set by the caller), no entropy / plane / RGB-row scratch.
 // png = true: a PNG sample: like a frame it resamples through the unfused passes, from RGB rows that
@@ -154,8 +140,10 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   // multi-hypothesis speculative pass for latency-mode baseline images without restart intervals;
   // only the 11-bit entropy routes launch it (k_entspec_mh), so images of more than 4 table slots
   // (kRtEnt10) keep the ordinary speculative pass
+  // (the table slots, counted once: they also choose the coefficient format; frames and PNGs have no scan)
+  const int slots = frames || png ? 2 * kMaxComp : huff_slots(*d);
   d->mh = (int8_t)(SDSJ_MH && d->lat && !d->progressive && d->restart_interval == 0 && d->bpm <= kMhMaxPhases &&
-                   huff_slots(*d) <= 4);
+                   slots <= 4);
   {
     const int64_t bits = d->entropy_len * 8;
     const int64_t per_group = (int64_t)kDecodeThreads * (d->lat ? kLatSubBits : kGroupBits);
@@ -192,7 +180,7 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   d->off_sub = take((int64_t)d->nsub_cap * sizeof(SubState));
   d->off_rec = take((int64_t)d->nsub_cap * kRec * sizeof(SyncRec));
   d->off_ptab = take(prog ? (int64_t)sizeof(ProgTables) : 0);
-  d->off_coef = take(d->total_blocks * 128);
+  d->off_coef = take(coef_bytes(*d, slots));
   int64_t planes = 0;
   for (int c = 0; c < d->ncomp; c++) planes += align_up((int64_t)d->comp[c].pitch * d->comp[c].bh * 8, 256);
   d->off_planes = take(planes);

@@ -44,10 +44,17 @@ def main():
     else:
         jpg = next(j for c, j, _ in G.g1() if c["name"] == name)
     eng = JpegEngine("cuda:0", max_batch=8)
+    from tests.coef_compact import blocks_differing_from_oracle, is_compact, read_blocks
+    # (stage_report's own coefficient lines read the 128-byte format only: tests/coef_compact.py reads both)
     for line in stage_report(eng, jpg):
-        print(line)
+        if not line.startswith("coef comp"):
+            print(line)
     d, fetch = snapshot(eng, 1)
     d = d[0]
+    zz, flagged = read_blocks(d, fetch)
+    print(f"coef format: {'compact' if is_compact(d) else 'int16'}, {int(flagged.sum())} of {len(zz)} blocks flagged")
+    for c, nbad in enumerate(blocks_differing_from_oracle(d, zz, jpg)):
+        print(f"coef comp{c}: {nbad} blocks differ")
     ref = unstuff_ref(jpg, d.entropy_off)
     got = fetch(d.off_ustream, d.ulen).tobytes()
     print(f"ustream: gpu {d.ulen} B, ref {len(ref)} B, nseg {d.nseg} found {d.useg_found}")
