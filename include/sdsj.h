@@ -62,7 +62,7 @@ extern "C" {
 
 typedef struct sdsj_info {
     int32_t width, height; /* image size (PIL Image.size order: width, height) */
-    int32_t ncomp;         /* 1 (grayscale) or 3 (YCbCr) */
+    int32_t ncomp;         /* 1 (grayscale) or 3 (YCbCr; RGB-coded under SDSJ_FORMAT_JPEG_EXT) */
     int32_t h_samp[3], v_samp[3];
     int32_t restart_interval;
     int32_t supported; /* 1 if the MI355X path decodes it */
@@ -90,6 +90,10 @@ int sdsj_abi_version(void);
 /* Host-side header parse of one JPEG (no GPU needed). */
 int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out);
 
+/* The same for an engine whose format mask is `formats` (it must have SDSJ_FORMAT_JPEG): with
+ * SDSJ_FORMAT_JPEG_EXT (below) the wider subset is `supported`; without it the result is sdsj_probe's. */
+int sdsj_probe_formats(const uint8_t* jpg, size_t n, int formats, sdsj_info* out);
+
 /* Device scratch one JPEG needs for `op` (host planning, no GPU): *need = bytes (256-aligned share of
  * the engine's scratch).  Returns the header status (SDSJ_OK, SDSJ_UNSUPPORTED, SDSJ_CORRUPT); a
  * batch on the device-resident entry point needs the sum over its samples (sdsj_engine_reserve). */
@@ -115,11 +119,24 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * pHYs, iCCP, zTXt, iTXt; with SDSJ_FORMAT_PNG_EXT also eXIf and the ancillary chunks PIL has no handler
  * for).  A compressed chunk is accepted only where its zlib stream is well formed and inflates to fewer than
  * 1,048,576 bytes (PIL raises above that), the text chunks of a file only up to 67,108,864 bytes in all
- * (PIL's limit); everything else, and APNG, stays SDSJ_UNSUPPORTED.  Without the bit nothing changes. */
+ * (PIL's limit); everything else, and APNG, stays SDSJ_UNSUPPORTED.  Without the bit nothing changes.
+ *
+ * SDSJ_FORMAT_JPEG_EXT (valid only together with SDSJ_FORMAT_JPEG, SDSJ_EINVAL otherwise; it combines freely
+ * with the PNG bits) widens the three-component JPEG subset, baseline and progressive alike: every
+ * sampling whose factors divide the largest (upsampling ratios 1..4 per axis and component: 4:1:1, 4:1:0,
+ * 1x4, 3x1, 2x3, 2x4, a subsampled first component, mixed ratios; at most 10 blocks per MCU as before),
+ * upsampled as libjpeg's jinit_upsampler chooses per component (fancy h2v1 / h2v2 / h1v2 as before, every
+ * other ratio by replication, int_upsample), and RGB-coded files -- those libjpeg's
+ * default_decompress_parms takes as JCS_RGB: no JFIF marker and an Adobe marker with transform 0, or
+ * neither marker and the component ids 'R', 'G', 'B' -- whose planes are stored as R, G, B without a
+ * colour transform.  Fractional ratios, four components (CMYK / YCCK), multi-scan sequential, arithmetic
+ * and 12-bit files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: those files report
+ * SDSJ_UNSUPPORTED. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
 #define SDSJ_FORMAT_PNG_EXT 4
 #define SDSJ_FORMAT_PNG_META 16
+#define SDSJ_FORMAT_JPEG_EXT 64
 
 typedef struct sdsj_png_info {
     int32_t width, height;

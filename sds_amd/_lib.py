@@ -34,21 +34,24 @@ EXPORTS = [
     "sdsj_stage_name", "sdsj_engine_debug_buffers", "sdsj_resize_frames_device", "sdsj_submit_batch",
     "sdsj_submit_files", "sdsj_wait_batch", "sdsj_engine_counters", "sdsj_counter_name", "sdsj_engine_set_lanes",
     "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve", "sdsj_engine_set_formats", "sdsj_png_probe",
-    "sdsj_plan_need_formats", "sdsj_png_probe_formats",
+    "sdsj_plan_need_formats", "sdsj_png_probe_formats", "sdsj_probe_formats",
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
-FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META = 1, 2, 4, 16  # SDSJ_FORMAT_*
+FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META, FORMAT_JPEG_EXT = 1, 2, 4, 16, 64  # SDSJ_FORMAT_*
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
 # valid only together with PNG, so the name carries both
 # "png-meta": PNG files as converters and editors write them (iCCP, zTXt, iTXt, chunks after the image data);
 # likewise valid only together with PNG, and combinable with "png-ext"
+# "jpeg-ext": JPEG with the wider three-component subset (upsampling ratios of 3 and 4 such as 4:1:1 and 4:1:0,
+# RGB-coded files); the bit is valid only together with JPEG, so the name carries both
 FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT,
-           "png-meta": FORMAT_PNG | FORMAT_PNG_META}
+           "png-meta": FORMAT_PNG | FORMAT_PNG_META, "jpeg-ext": FORMAT_JPEG | FORMAT_JPEG_EXT}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 def format_mask(formats) -> int:
-    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "png" / "png-ext" / "png-meta" (None: JPEG only, the engine's default)."""
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "png" / "png-ext" / "png-meta" (None: JPEG only, the
+    engine's default).  "jpeg-ext" includes "jpeg", as "png-ext" and "png-meta" include "png"."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):
@@ -117,6 +120,7 @@ def load() -> ctypes.CDLL:
         vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
         lib.sdsj_abi_version.restype = ctypes.c_int
         lib.sdsj_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjInfo)]
+        lib.sdsj_probe_formats.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, ctypes.POINTER(SdsjInfo)]
         lib.sdsj_engine_create.argtypes = [ctypes.c_int, ctypes.POINTER(SdsjCfg), ctypes.POINTER(vp)]
         lib.sdsj_engine_destroy.argtypes = [vp]
         lib.sdsj_decode_resize_batch.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p),
@@ -160,9 +164,14 @@ def load() -> ctypes.CDLL:
         return lib
 
 
-def probe(jpg: bytes) -> tuple[int, SdsjInfo]:
+def probe(jpg: bytes, mask=None) -> tuple[int, SdsjInfo]:
+    """``mask``: the SDSJ_FORMAT_* mask the sample will be decoded under (sdsj_probe_formats: with
+    FORMAT_JPEG_EXT the wider JPEG subset is supported); None: the default subset (sdsj_probe)."""
     info = SdsjInfo()
-    st = load().sdsj_probe(jpg, len(jpg), ctypes.byref(info))
+    if mask is None:
+        st = load().sdsj_probe(jpg, len(jpg), ctypes.byref(info))
+    else:
+        st = load().sdsj_probe_formats(jpg, len(jpg), int(mask), ctypes.byref(info))
     return st, info
 
 

@@ -5,7 +5,8 @@
 // 8-bit sequential with one interleaved scan holding every component, SOF2 progressive -- whose
 // scans k_prog parses --, Huffman coding, optional DRI): the decoder Pillow calls from
 // sds/transforms/functional.py:100.  Everything else is reported as SDSJ_UNSUPPORTED (non-JPEG
-// input, lossless, arithmetic, 12-bit, CMYK, Adobe-RGB, multi-scan sequential).
+// input, lossless, arithmetic, 12-bit, CMYK, multi-scan sequential; RGB-coded files and upsampling
+// ratios above 2 too, unless the engine's mask has SDSJ_FORMAT_JPEG_EXT: setup_geometry).
 #pragma once
 #include <stdint.h>
 
@@ -130,7 +131,7 @@ SDSJ_HD inline bool huff_table_ok(const HuffSpec& h, bool dc) {
 
 struct CompDesc {
   int32_t h, v, tq, td, ta;
-  int32_t rh, rv;     // upsampling ratio hmax/h, vmax/v (1 or 2)
+  int32_t rh, rv;     // upsampling ratio hmax/h, vmax/v (1 or 2; 1..4 under SDSJ_FORMAT_JPEG_EXT)
   int32_t dw, dh;     // downsampled width / height (jdinput.c)
   int32_t bw, bh;     // coded blocks per row / column (MCU padded when interleaved)
   int32_t pitch;      // plane row pitch in bytes (bw * 8)
@@ -567,24 +568,37 @@ SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t,
   }
 }
 
-// Colour space (jdapimin.c default_decompress_parms) and geometry (jdinput.c).
-SDSJ_HD inline int setup_geometry(ImgDesc* d, const ImgTables* t) {
-  if (d->ncomp == 3) {
-    if (!d->saw_jfif) {
-      if (d->saw_adobe) {
-        if (d->adobe_transform == 0) return SDSJ_UNSUPPORTED;  // Adobe RGB
-      } else if (d->comp_id[0] == 82 && d->comp_id[1] == 71 && d->comp_id[2] == 66) {
-        return SDSJ_UNSUPPORTED;  // 'R','G','B' component ids
-      }
-    }
-  }
+// A three-component image libjpeg takes as JCS_RGB (jdapimin.c default_decompress_parms: JFIF wins over
+// everything, otherwise an Adobe marker with transform 0, otherwise the component ids 'R','G','B'): its
+// planes are R, G, B, stored without a colour transform (jdcolor.c rgb_rgb_convert).  Decoded only under
+// SDSJ_FORMAT_JPEG_EXT (setup_geometry); the planner and k_color ask the descriptor's header fields.
+SDSJ_HD inline bool rgb_coded(const ImgDesc& d) {
+  if (d.ncomp != 3 || d.saw_jfif) return false;
+  if (d.saw_adobe) return d.adobe_transform == 0;
+  return d.comp_id[0] == 82 && d.comp_id[1] == 71 && d.comp_id[2] == 66;
+}
+
+// An image only SDSJ_FORMAT_JPEG_EXT decodes: RGB-coded, or some component upsampled by a ratio above 2
+// (jdsample.c int_upsample).  Such an image takes the unfused colour / resample passes (plan_image): the
+// fused kernels convert YCbCr and assume ratios of 1 or 2.
+SDSJ_HD inline bool jpeg_ext_image(const ImgDesc& d) {
+  bool wide = false;
+  for (int c = 0; c < d.ncomp; c++) wide |= d.comp[c].rh > 2 || d.comp[c].rv > 2;
+  return wide || rgb_coded(d);
+}
+
+// Colour space (jdapimin.c default_decompress_parms) and geometry (jdinput.c).  formats: the engine's
+// SDSJ_FORMAT_* mask; SDSJ_FORMAT_JPEG_EXT admits RGB-coded images and upsampling ratios of 3 and 4.
+SDSJ_HD inline int setup_geometry(ImgDesc* d, const ImgTables* t, int formats = SDSJ_FORMAT_JPEG) {
+  const bool ext = (formats & SDSJ_FORMAT_JPEG_EXT) != 0;
+  if (rgb_coded(*d) && !ext) return SDSJ_UNSUPPORTED;  // Adobe RGB, or 'R','G','B' component ids
   int bpm = 0;
   for (int c = 0; c < d->ncomp; c++) {
     CompDesc& cp = d->comp[c];
     if (d->hmax % cp.h || d->vmax % cp.v) return SDSJ_UNSUPPORTED;
     cp.rh = d->hmax / cp.h;
     cp.rv = d->vmax / cp.v;
-    if (cp.rh > 2 || cp.rv > 2) return SDSJ_UNSUPPORTED;
+    if ((cp.rh > 2 || cp.rv > 2) && !ext) return SDSJ_UNSUPPORTED;
     cp.dw = ceil_div(d->width * cp.h, d->hmax);
     cp.dh = ceil_div(d->height * cp.v, d->vmax);
     if (d->progressive) continue;  // tables are checked per scan (k_prog)

@@ -638,13 +638,15 @@ int sdsj_wait_batch(sdsj_engine* e, int slot, int32_t* status) {
   return stage_collect(e, e->slots[slot], status);
 }
 
-int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out) {
-  if (!jpg || !out) return SDSJ_EINVAL;
+int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out) { return sdsj_probe_formats(jpg, n, SDSJ_FORMAT_JPEG, out); }
+
+int sdsj_probe_formats(const uint8_t* jpg, size_t n, int formats, sdsj_info* out) {
+  if (!jpg || !out || !(formats & SDSJ_FORMAT_JPEG)) return SDSJ_EINVAL;
   memset(out, 0, sizeof(*out));
   ImgDesc d;
   static thread_local ImgTables t;
   MemReader rd{jpg};
-  int st = parse_sample(rd, (int64_t)n, &d, &t, CopySink<MemReader>{rd});
+  int st = parse_sample(rd, (int64_t)n, &d, &t, CopySink<MemReader>{rd}, formats);
   out->width = d.width;
   out->height = d.height;
   out->ncomp = d.ncomp;
@@ -667,11 +669,13 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
   return st;
 }
 
-// A format mask names at least one of JPEG and PNG, nothing unknown, and PNG_EXT and PNG_META (alone or
-// together) only with PNG.
+// A format mask names at least one of JPEG and PNG, nothing unknown, PNG_EXT and PNG_META (alone or
+// together) only with PNG, and JPEG_EXT only with JPEG.
 static bool valid_formats(int mask) {
-  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | sub;
-  return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG));
+  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META;
+  const int all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | sub | SDSJ_FORMAT_JPEG_EXT;
+  return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
+         (!(mask & SDSJ_FORMAT_JPEG_EXT) || (mask & SDSJ_FORMAT_JPEG));
 }
 
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need) {

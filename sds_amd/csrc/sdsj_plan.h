@@ -116,6 +116,9 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
     }
   }
   if (frames || png) d->fused = 0;
+  // SDSJ_FORMAT_JPEG_EXT images (RGB-coded, or a ratio above 2): the unfused passes, whose k_color
+  // restates every upsampling method and the missing colour transform
+  else if (jpeg_ext_image(*d)) d->fused = 0;
   // specialised fused kernels (sdsj_resample420.hip): 4:2:0 (h2v2 fancy chroma), 4:2:2 (h2v1 fancy
   // chroma), 4:4:4 and grayscale, horizontal and vertical passes, odd tap counts 3..11; everything
   // else takes the generic k_resample
@@ -214,9 +217,10 @@ SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
 
 // JPEG headers up to the first SOS, then colour space and geometry.
 template <class Reader, class Sink>
-SDSJ_HD int parse_sample(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, const Sink& sink) {
+SDSJ_HD int parse_sample(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, const Sink& sink,
+                         int formats = SDSJ_FORMAT_JPEG) {
   int st = parse_headers(rd, n, d, t, sink);
-  if (st == SDSJ_OK) st = setup_geometry(d, t);
+  if (st == SDSJ_OK) st = setup_geometry(d, t, formats);
   return st;
 }
 
@@ -246,7 +250,7 @@ SDSJ_HD int plan_sample(const Reader& rd, int64_t n, const sdsj_op& op, bool sma
   } else if (!(formats & SDSJ_FORMAT_JPEG)) {
     status = SDSJ_UNSUPPORTED;
   } else {
-    status = parse_sample(rd, n, d, t, sink);
+    status = parse_sample(rd, n, d, t, sink, formats);
     if (status == SDSJ_OK) plan_image(d, op, false, small);
   }
   return status;

@@ -1,7 +1,7 @@
 // sdsj_unfused.hip -- gfx950 (MI355X) kernels of the unfused colour and resample passes.
 //
 // Stage map (reference behaviour each kernel reproduces, see DESIGN.md for the layout/rooflines):
-//   k_color    fancy upsampling + YCbCr->RGB      jdsample.c / jdmainct.c / jdcolor.c
+//   k_color    upsampling + YCbCr->RGB (or RGB kept) jdsample.c / jdmainct.c / jdcolor.c
 //   k_coeffs   resampling tables (doubles)        Pillow Resample.c precompute_coeffs
 //   k_hpass    horizontal pass, uint8 out         Pillow ImagingResampleHorizontal_8bpc
 //   k_vpass    vertical pass + hflip + layout/LUT Pillow ImagingResampleVertical_8bpc,
@@ -19,11 +19,19 @@
 namespace sdsj {
 
 // ------------------------------------------------------------------------------------------
-// k_color: fancy upsampling (jdsample.c, context rows per jdmainct.c) + ycc_rgb_convert.
+// k_color: upsampling (jdsample.c, context rows per jdmainct.c) + ycc_rgb_convert, or no conversion
+// for an RGB-coded image.
 // One thread per RGB pixel of rows [src_y0, src_y1) x cols [src_x0, src_x0 + src_w).
 // ------------------------------------------------------------------------------------------
+// v / r for an upsampling ratio r = 1..4 (jdsample.c int_upsample's replication): shifts, or a
+// multiplication by the constant reciprocal for 3 -- no division by a variable.
+__device__ __forceinline__ int ratio_div(int v, int r) { return r == 1 ? v : r == 2 ? v >> 1 : r == 4 ? v >> 2 : v / 3; }
+
+// jdsample.c jinit_upsampler, per component: copy (1, 1), the fancy methods for (2, 1), (2, 2) and (1, 2),
+// int_upsample for every other ratio (a 3 or 4 on either axis; SDSJ_FORMAT_JPEG_EXT images only).
 __device__ __forceinline__ int up_sample(const uint8_t* P, const CompDesc& c, int x, int y) {
   if (c.rh == 1 && c.rv == 1) return P[(int64_t)y * c.pitch + x];
+  if (c.rh > 2 || c.rv > 2) return P[(int64_t)ratio_div(y, c.rv) * c.pitch + ratio_div(x, c.rh)];  // int_upsample
   const int dw = c.dw, dh = c.dh;
   if (c.rv == 2) {
     const int i = y >> 1;
@@ -81,6 +89,7 @@ __global__ void __launch_bounds__(256) k_color(int n, const ImgDesc* __restrict_
   const int64_t total = (int64_t)w * h;
   const uint8_t* planes = scratch + d->off_planes;
   uint8_t* rgb = scratch + d->off_rgb;
+  const bool rgbc = rgb_coded(*d);  // the planes are R, G, B (jdcolor.c rgb_rgb_convert)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int yy = (int)(i / w), xx = (int)(i - (int64_t)yy * w);
     const int x = d->src_x0 + xx, y = d->src_y0 + yy;
@@ -91,7 +100,13 @@ __global__ void __launch_bounds__(256) k_color(int n, const ImgDesc* __restrict_
     } else {
       const int cb = up_sample(planes + d->comp[1].plane_off, d->comp[1], x, y);
       const int cr = up_sample(planes + d->comp[2].plane_off, d->comp[2], x, y);
-      ycc_to_rgb(Y, cb, cr, &R, &G, &B);
+      if (rgbc) {
+        R = (uint32_t)Y;
+        G = (uint32_t)cb;
+        B = (uint32_t)cr;
+      } else {
+        ycc_to_rgb(Y, cb, cr, &R, &G, &B);
+      }
     }
     uint8_t* o = rgb + i * 3;
     o[0] = (uint8_t)R;

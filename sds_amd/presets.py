@@ -193,7 +193,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     never initialise HIP themselves.  ``None`` = every process creates its own engine (device outputs,
     reaching the parent through HIP IPC); a string = the address of a running service.
 
-    ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` /
+    ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` /
     ``"png"`` / ``"png-ext"`` / ``"png-meta"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
@@ -210,8 +210,14 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     compressed chunk that inflates to more than 1 MiB, more than 64 MiB of text) and compressed chunks whose zlib
     stream is damaged still rerun on PIL.  Plain files decode 9 % slower under this mask than under ``"png"`` (5.9k
     against 6.5k images/s, ``profiles/png_meta_bench.jsonl``), files with such chunks at 5.6k against 0.31k on PIL.
-    In a served worker process (the decode service) PNG samples keep the PIL route whatever this says: the
-    service's wire protocol carries no format mask.
+    ``"jpeg-ext"`` (it includes ``"jpeg"`` and combines with the PNG names) widens the three-component JPEG subset:
+    every sampling whose factors divide the largest -- 4:1:1, 4:1:0, 1x4, 3x1, 2x3, 2x4, a subsampled first
+    component, mixed ratios -- upsampled as libjpeg does (ratios of 3 and 4 by replication), and RGB-coded files
+    (an Adobe marker with transform 0, or component ids ``R`` ``G`` ``B``; Pillow's ``keep_rgb=True``), baseline and
+    progressive.  Those images take the unfused colour / resample kernels; every other JPEG decodes exactly as
+    without the name.  CMYK / YCCK, multi-scan sequential, arithmetic and 12-bit files still rerun on PIL.
+    In a served worker process (the decode service) PNG and ``"jpeg-ext"`` samples keep the PIL route whatever this
+    says: the service's wire protocol carries no format mask.
     """
 
     def __init__(self, input_field: str, output_field: Optional[str] = None, resolution=(256, 256),
@@ -258,6 +264,8 @@ class GpuDecodeResizeImageTransform(BaseTransform):
             mask = _lib.format_mask(self.gpu_formats)
             if eng is not None and mask & _lib.FORMAT_PNG and data[:8] == _lib.PNG_SIGNATURE:
                 st, info = _lib.png_probe(data, mask)  # (under the mask: a "png-ext" file is sized natively)
+            elif eng is not None and mask & _lib.FORMAT_JPEG_EXT:
+                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" file is sized natively)
             else:
                 st, info = _lib.probe(data)
             if st != _lib.OK or info.width <= 0 or info.height <= 0:  # not a JPEG this path decodes
@@ -550,7 +558,8 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"png"``, ``"png-ext"`` or ``"png-meta"`` to opt in; see GpuDecodeResizeImageTransform).
+    formats decoded natively (add ``"jpeg-ext"``, ``"png"``, ``"png-ext"`` or ``"png-meta"`` to opt in; see
+    GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
     the pipeline gets device tensors (it decodes in-process), while its forked DataLoader workers get
