@@ -91,7 +91,8 @@ int sdsj_abi_version(void);
 int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out);
 
 /* The same for an engine whose format mask is `formats` (it must have SDSJ_FORMAT_JPEG): with
- * SDSJ_FORMAT_JPEG_EXT (below) the wider subset is `supported`; without it the result is sdsj_probe's. */
+ * SDSJ_FORMAT_JPEG_EXT or SDSJ_FORMAT_JPEG_SCANS (below) the files those bits admit are `supported`; without
+ * them the result is sdsj_probe's. */
 int sdsj_probe_formats(const uint8_t* jpg, size_t n, int formats, sdsj_info* out);
 
 /* Device scratch one JPEG needs for `op` (host planning, no GPU): *need = bytes (256-aligned share of
@@ -129,14 +130,26 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * other ratio by replication, int_upsample), and RGB-coded files -- those libjpeg's
  * default_decompress_parms takes as JCS_RGB: no JFIF marker and an Adobe marker with transform 0, or
  * neither marker and the component ids 'R', 'G', 'B' -- whose planes are stored as R, G, B without a
- * colour transform.  Fractional ratios, four components (CMYK / YCCK), multi-scan sequential, arithmetic
- * and 12-bit files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: those files report
- * SDSJ_UNSUPPORTED. */
+ * colour transform.  Fractional ratios, four components (CMYK / YCCK), arithmetic and 12-bit files stay
+ * SDSJ_UNSUPPORTED.  Without the bit nothing changes: those files report SDSJ_UNSUPPORTED.
+ *
+ * SDSJ_FORMAT_JPEG_SCANS (valid only together with SDSJ_FORMAT_JPEG, SDSJ_EINVAL otherwise; it combines freely
+ * with SDSJ_FORMAT_JPEG_EXT and the PNG bits) accepts multi-scan sequential files: 8-bit SOF0 / SOF1 frames of
+ * three components whose components arrive in more than one scan (Y, Cb, Cr one after another, Y then
+ * Cb + Cr, any order and grouping; jpegtran -scans writes them), with or without restart intervals, with
+ * DHT / DQT / DRI segments between the scans, each component's quantisation table latched at its first scan.
+ * Every scan must be a full sequential one (Ss = 0, Se = 63, Ah = Al = 0) and code components no earlier scan
+ * coded: a file that breaks either rule reports SDSJ_UNSUPPORTED (libjpeg only warns and overlays the
+ * coefficients), a scan without restart intervals that holds fill bytes before a stuffed zero SDSJ_CORRUPT.
+ * A file that ends at EOI before every component was coded decodes, the missing components from zero
+ * coefficients, as in PIL.  Samplings with ratios of 3 and 4 and RGB-coded files need SDSJ_FORMAT_JPEG_EXT as
+ * well.  Without the bit nothing changes: multi-scan sequential files report SDSJ_UNSUPPORTED. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
 #define SDSJ_FORMAT_PNG_EXT 4
 #define SDSJ_FORMAT_PNG_META 16
 #define SDSJ_FORMAT_JPEG_EXT 64
+#define SDSJ_FORMAT_JPEG_SCANS 128
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -155,7 +168,10 @@ int sdsj_png_probe(const uint8_t* png, size_t n, sdsj_png_info* out);
 int sdsj_png_probe_formats(const uint8_t* png, size_t n, int formats, sdsj_png_info* out);
 
 /* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
- * has SDSJ_FORMAT_PNG (a format outside the mask reports SDSJ_UNSUPPORTED, need 0). */
+ * has SDSJ_FORMAT_PNG (a format outside the mask reports SDSJ_UNSUPPORTED, need 0).  With
+ * SDSJ_FORMAT_JPEG_SCANS a multi-scan sequential file that is refused over its scans (not its header: a scan that
+ * is not a sequential one, a component coded twice, fill bytes before a stuffed zero) reports that status together
+ * with the bytes the device plans for it before it refuses it: a batch that holds the file needs them. */
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need);
 
 /* Creates an engine bound to HIP device `hip_device`.  Scratch memory is owned by the engine.  An engine

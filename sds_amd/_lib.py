@@ -38,20 +38,24 @@ EXPORTS = [
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
 FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META, FORMAT_JPEG_EXT = 1, 2, 4, 16, 64  # SDSJ_FORMAT_*
+FORMAT_JPEG_SCANS = 128
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
 # valid only together with PNG, so the name carries both
 # "png-meta": PNG files as converters and editors write them (iCCP, zTXt, iTXt, chunks after the image data);
 # likewise valid only together with PNG, and combinable with "png-ext"
 # "jpeg-ext": JPEG with the wider three-component subset (upsampling ratios of 3 and 4 such as 4:1:1 and 4:1:0,
 # RGB-coded files); the bit is valid only together with JPEG, so the name carries both
+# "jpeg-scans": multi-scan sequential JPEG (SOF0 / SOF1 frames whose components arrive in more than one scan, as
+# jpegtran -scans writes them); likewise valid only together with JPEG, and combinable with "jpeg-ext"
 FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT,
-           "png-meta": FORMAT_PNG | FORMAT_PNG_META, "jpeg-ext": FORMAT_JPEG | FORMAT_JPEG_EXT}
+           "png-meta": FORMAT_PNG | FORMAT_PNG_META, "jpeg-ext": FORMAT_JPEG | FORMAT_JPEG_EXT,
+           "jpeg-scans": FORMAT_JPEG | FORMAT_JPEG_SCANS}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 def format_mask(formats) -> int:
-    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "png" / "png-ext" / "png-meta" (None: JPEG only, the
-    engine's default).  "jpeg-ext" includes "jpeg", as "png-ext" and "png-meta" include "png"."""
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "png" / "png-ext" / "png-meta" (None: JPEG
+    only, the engine's default).  "jpeg-ext" and "jpeg-scans" include "jpeg", as "png-ext" and "png-meta" include "png"."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):
@@ -166,7 +170,8 @@ def load() -> ctypes.CDLL:
 
 def probe(jpg: bytes, mask=None) -> tuple[int, SdsjInfo]:
     """``mask``: the SDSJ_FORMAT_* mask the sample will be decoded under (sdsj_probe_formats: with
-    FORMAT_JPEG_EXT the wider JPEG subset is supported); None: the default subset (sdsj_probe)."""
+    FORMAT_JPEG_EXT the wider JPEG subset is supported, with FORMAT_JPEG_SCANS multi-scan sequential files); None: the
+    default subset (sdsj_probe)."""
     info = SdsjInfo()
     if mask is None:
         st = load().sdsj_probe(jpg, len(jpg), ctypes.byref(info))

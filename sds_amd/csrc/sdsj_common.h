@@ -5,8 +5,9 @@
 // 8-bit sequential with one interleaved scan holding every component, SOF2 progressive -- whose
 // scans k_prog parses --, Huffman coding, optional DRI): the decoder Pillow calls from
 // sds/transforms/functional.py:100.  Everything else is reported as SDSJ_UNSUPPORTED (non-JPEG
-// input, lossless, arithmetic, 12-bit, CMYK, multi-scan sequential; RGB-coded files and upsampling
-// ratios above 2 too, unless the engine's mask has SDSJ_FORMAT_JPEG_EXT: setup_geometry).
+// input, lossless, arithmetic, 12-bit, CMYK; RGB-coded files and upsampling ratios above 2 too,
+// unless the engine's mask has SDSJ_FORMAT_JPEG_EXT: setup_geometry; multi-scan sequential files
+// too, unless it has SDSJ_FORMAT_JPEG_SCANS: parse_headers hands their scans to k_scans).
 #pragma once
 #include <stdint.h>
 
@@ -139,6 +140,7 @@ struct CompDesc {
 };
 
 enum GeoMode : int32_t { kGeoResize = 0, kGeoIdentity = 1, kGeoZeros = 2 };
+constexpr int32_t kScansSequential = 2;  // ImgDesc::progressive of a multi-scan sequential file (1: SOF2)
 
 struct ImgDesc {
   int32_t status;
@@ -200,7 +202,10 @@ struct ImgDesc {
   int32_t rgb_pitch;   // pixels per row of the RGB rows the unfused passes read (frames: the frame width)
   int32_t ent_groups;  // workgroups sharing the image's subsequences in the spec / write passes
   // progressive JPEG (SOF2): every scan is decoded by k_prog from sos_pos (the first SOS segment's
-  // length field) into the zeroed coefficient array; ProgTables at off_ptab hold its table state
+  // length field) into the zeroed coefficient array; ProgTables at off_ptab hold its table state.
+  // kScansSequential (2): a multi-scan sequential file (SOF0 / SOF1, SDSJ_FORMAT_JPEG_SCANS), walked
+  // from sos_pos the same way by k_scans -- everything that asks "progressive != 0" (no unstuffed
+  // stream, int16 coefficient blocks, tables checked per scan) holds for it as it stands
   int32_t progressive;
   int32_t lat;  // latency-mode plan (kSmallBatch)
   int64_t sos_pos;
@@ -327,6 +332,7 @@ enum Route : int32_t {
   kRtEnt11G,                      // (count only) (image, group) tasks of the kRtEnt11M images: group_tasks()
   kRtUsSmall, kRtUsBig,           // unstuffing: k_us_serial / the tile-parallel passes (kUsSerialTiles)
   kRtPng,                         // PNG samples (k_png_inflate, k_png_unfilter); they resample through kRtUnfused
+  kRtScans,                       // multi-scan sequential images (k_scans; ImgDesc::progressive == kScansSequential)
   kNumRoutes
 };
 constexpr int kRouteSlots = 48;  // counts [0, kNumRoutes), the rest zero
@@ -421,8 +427,11 @@ struct CopySink {
 
 // Parses markers up to the first SOS (jdmarker.c subset).  `rd(i)` returns byte i; `t` must be
 // non-null (no null checks: on the device it points into LDS).  Bulk table bytes go through `sink`.
+// formats: the engine's SDSJ_FORMAT_* mask; with SDSJ_FORMAT_JPEG_SCANS a sequential frame of three
+// components whose first SOS names fewer of them is accepted as kScansSequential.
 template <class Reader, class Sink>
-SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, const Sink& sink) {
+SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, const Sink& sink,
+                          int formats = SDSJ_FORMAT_JPEG) {
   d->status = SDSJ_OK;
   d->width = d->height = d->ncomp = 0;
   d->progressive = 0;
@@ -539,6 +548,13 @@ SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t,
         int ns = rd(s);
         if (ns < 1 || ns > 4 || sl != 2 * ns + 4) return SDSJ_CORRUPT;  // get_sos: JERR_BAD_LENGTH
         if (d->progressive) {  // every scan is parsed by k_prog
+          d->sos_pos = i;
+          d->entropy_off = i + len;
+          d->entropy_len = n - d->entropy_off;
+          return SDSJ_OK;
+        }
+        if (ns < d->ncomp && d->ncomp == 3 && (formats & SDSJ_FORMAT_JPEG_SCANS)) {  // every scan is parsed by k_scans
+          d->progressive = kScansSequential;
           d->sos_pos = i;
           d->entropy_off = i + len;
           d->entropy_len = n - d->entropy_off;

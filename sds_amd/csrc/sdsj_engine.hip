@@ -230,6 +230,8 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   mark(3);
   // (after mark 3: the next lane may start while this lane's progressive images decode)
   SDSJ_HIP(e, launch_prog(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
+  if (e->formats & SDSJ_FORMAT_JPEG_SCANS)  // (counts under the progressive stage)
+    SDSJ_HIP(e, launch_scans(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (evs) (void)hipEventRecord((*evs)[kPngEvent].get(), s);
   if (e->formats & SDSJ_FORMAT_PNG)
     SDSJ_HIP(e, launch_png(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint,
@@ -651,6 +653,7 @@ int sdsj_probe_formats(const uint8_t* jpg, size_t n, int formats, sdsj_info* out
   out->height = d.height;
   out->ncomp = d.ncomp;
   if (st == SDSJ_OK && !scan_tables_ok(d, t)) st = SDSJ_CORRUPT;
+  if (st == SDSJ_OK && d.progressive == kScansSequential) st = scans_check(rd, (int64_t)n, d);
   for (int c = 0; c < d.ncomp && c < 3; c++) {
     out->h_samp[c] = d.comp[c].h;
     out->v_samp[c] = d.comp[c].v;
@@ -670,20 +673,22 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 }
 
 // A format mask names at least one of JPEG and PNG, nothing unknown, PNG_EXT and PNG_META (alone or
-// together) only with PNG, and JPEG_EXT only with JPEG.
+// together) only with PNG, and JPEG_EXT and JPEG_SCANS (alone or together) only with JPEG.
 static bool valid_formats(int mask) {
-  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META;
-  const int all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | sub | SDSJ_FORMAT_JPEG_EXT;
+  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS;
+  const int all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | sub | jsub;
   return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
-         (!(mask & SDSJ_FORMAT_JPEG_EXT) || (mask & SDSJ_FORMAT_JPEG));
+         (!(mask & jsub) || (mask & SDSJ_FORMAT_JPEG));
 }
 
 int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int formats, int64_t* need) {
   if (!img || !need || !valid_op(op) || !valid_formats(formats)) return SDSJ_EINVAL;
-  int st = SDSJ_OK;
-  const int64_t b = host_plan_need(img, (int64_t)n, *op, &st, nullptr, false, formats);
+  int st = SDSJ_OK, later = SDSJ_OK;
+  const int64_t b = host_plan_need(img, (int64_t)n, *op, &st, nullptr, false, formats, &later);
   *need = st == SDSJ_OK ? align_up(b, 256) : 0;
-  return st;
+  // (a multi-scan file refused over its scans: the device plans its scratch before k_scans refuses it, so a batch
+  // that holds it needs these bytes)
+  return st == SDSJ_OK ? later : st;
 }
 
 int sdsj_engine_set_formats(sdsj_engine* e, int mask) {

@@ -1,5 +1,5 @@
 // sdsj_kernels.h -- launchers of every stage file's gfx950 kernels (sdsj_plan.hip, sdsj_unstuff.hip,
-// sdsj_entropy.hip, sdsj_progressive.hip, sdsj_png.hip, sdsj_png_ext.hip, sdsj_idct.hip, sdsj_unfused.hip, sdsj_resample.hip,
+// sdsj_entropy.hip, sdsj_progressive.hip, sdsj_scans.hip, sdsj_png.hip, sdsj_png_ext.hip, sdsj_idct.hip, sdsj_unfused.hip, sdsj_resample.hip,
 // sdsj_resample420.hip) and host-side planning (sdsj_plan.hip); engine-internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -59,6 +59,14 @@ hipError_t launch_scanmap(int n, const uint8_t* blob, const int64_t* offsets, Im
 hipError_t launch_prog(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
                        const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                        uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
+// k_prog_zero (sdsj_progressive.hip) over the images of route rt (kRtProg or kRtScans): their int16 coefficient arrays zeroed
+void launch_coef_zero(int rt, int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+                      uint64_t hint);
+// multi-scan sequential images (route kRtScans; engines with SDSJ_FORMAT_JPEG_SCANS): zero their coefficients, then
+// one wave per image decodes every scan (sdsj_scans.hip)
+hipError_t launch_scans(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
+                        const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+                        uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
 size_t enttab_bytes();  // per-image decode tables (k_enttab) held in HBM between the entropy kernels
 // k_enttab (decode tables) + k_entspec (subsequence layout, warm-up, speculative decode)
 // (small: a host-path latency-mode chunk, where ImgDesc::mh images take the multi-hypothesis pass)
@@ -95,8 +103,11 @@ hipError_t launch_finish(int n, ImgDesc* descs, const sdsj_op& op, void* out, in
 // *routes (optional): the routes the image takes (bits as in route masks; all of them when the host
 // parse fails, so the device's own verdict is never starved of a kernel)
 // small: the latency-mode plan of a chunk of at most kSmallBatch images (k_parse's `small`)
+// *later (optional): the status the device reports for the sample after planning where host planning knows it
+// (a multi-scan sequential file k_scans refuses, scans_check; SDSJ_OK otherwise): the sample is sized and routed
+// like a good one, as the device sizes it
 int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* status, uint64_t* routes = nullptr,
-                       bool small = false, int formats = SDSJ_FORMAT_JPEG);
+                       bool small = false, int formats = SDSJ_FORMAT_JPEG, int* later = nullptr);
 // host-side planning of one raw RGB frame (width x height) for the unfused passes; returns scratch bytes
 int64_t host_plan_frame(ImgDesc* d, int width, int height, const sdsj_op& op);
 }  // namespace sdsj

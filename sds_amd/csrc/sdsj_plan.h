@@ -209,7 +209,7 @@ SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
   }
   const int ns = huff_slots(d);
   *ru = d.progressive ? -1 : (d.ntiles > kUsSerialTiles || d.lat ? kRtUsBig : kRtUsSmall);
-  *re = d.progressive ? kRtProg : ns > 4 ? kRtEnt10 : (d.ent_groups > 1 ? kRtEnt11M : kRtEnt11);
+  *re = d.progressive == kScansSequential ? kRtScans : d.progressive ? kRtProg : ns > 4 ? kRtEnt10 : (d.ent_groups > 1 ? kRtEnt11M : kRtEnt11);
   *rr = d.geo == kGeoZeros ? -1
         : !d.fused ? kRtUnfused
                    : (d.rs_fast ? rs_route(d.rs_lay, d.rs_fast) : gen_route(d.need_h ? d.ksh : 1));
@@ -219,9 +219,68 @@ SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
 template <class Reader, class Sink>
 SDSJ_HD int parse_sample(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, const Sink& sink,
                          int formats = SDSJ_FORMAT_JPEG) {
-  int st = parse_headers(rd, n, d, t, sink);
+  int st = parse_headers(rd, n, d, t, sink, formats);
   if (st == SDSJ_OK) st = setup_geometry(d, t, formats);
   return st;
+}
+
+// The host's side of what k_scans refuses while it walks the scans of a multi-scan sequential file
+// (ImgDesc::progressive == kScansSequential): a scan that is not a full sequential one or codes a
+// component again (SDSJ_UNSUPPORTED: libjpeg only warns and overlays the coefficients), a malformed SOS
+// and, in a scan without restart intervals, fill bytes before a stuffed zero (SDSJ_CORRUPT: k_scans'
+// fill_stuffed).  A marker walk, no entropy decoding: host planning and the probe run it, so that such a file is
+// not sized as a decodable one; everything else about the stream is the device's verdict.
+template <class Reader>
+inline int scans_check(const Reader& rd, int64_t n, const ImgDesc& d) {
+  int64_t pos = d.sos_pos;
+  int restart_interval = d.restart_interval, coded = 0;
+  for (;;) {
+    if (pos + 2 > n) return SDSJ_CORRUPT;
+    const int len = (rd(pos) << 8) | rd(pos + 1);
+    if (len < 3 || pos + len > n) return SDSJ_CORRUPT;
+    const int ns = rd(pos + 2);
+    if (ns < 1 || ns > 4 || len != 2 * ns + 6) return SDSJ_CORRUPT;  // get_sos: JERR_BAD_LENGTH
+    for (int q = 0; q < ns; q++) {
+      const int cid = rd(pos + 3 + 2 * q);
+      int c = 0;
+      while (c < d.ncomp && d.comp_id[c] != cid) c++;
+      if (c == d.ncomp) return SDSJ_CORRUPT;
+      if ((coded >> c) & 1) return SDSJ_UNSUPPORTED;
+      coded |= 1 << c;
+    }
+    if (rd(pos + 3 + 2 * ns) != 0 || rd(pos + 4 + 2 * ns) != 63 || rd(pos + 5 + 2 * ns) != 0) return SDSJ_UNSUPPORTED;
+    // the scan's data, then the segments up to the next SOS
+    int64_t i = pos + len;
+    bool in_scan = true;
+    for (;;) {
+      while (i < n && rd(i) != 0xFF) i++;
+      int64_t j = i;
+      while (j < n && rd(j) == 0xFF) j++;
+      if (j >= n) return SDSJ_OK;  // (the input ends: the device reports it)
+      const int m = rd(j);
+      if (m == 0) {  // a stuffed zero
+        if (in_scan && j - i >= 2 && restart_interval == 0) return SDSJ_CORRUPT;
+        i = j + 1;
+        continue;
+      }
+      if ((m >= 0xD0 && m <= 0xD7) || m == 0x01) {
+        i = j + 1;
+        continue;
+      }
+      const bool seg = (m >= 0xE0 && m <= 0xEF) || m == 0xFE || m == 0xDD || m == 0xC4 || m == 0xDB || m == 0xDA;
+      if (!seg) return SDSJ_OK;  // EOI; anything else is the device's to refuse
+      in_scan = false;
+      if (j + 3 > n) return SDSJ_OK;
+      const int l2 = (rd(j + 1) << 8) | rd(j + 2);
+      if (l2 < 2 || j + 1 + l2 > n) return SDSJ_OK;
+      if (m == 0xDA) {
+        pos = j + 1;
+        break;
+      }
+      if (m == 0xDD && l2 == 4) restart_interval = (rd(j + 3) << 8) | rd(j + 4);
+      i = j + 1 + l2;
+    }
+  }
 }
 
 // Validation of the Huffman tables a baseline scan uses (huff_table_ok; a progressive image's are

@@ -242,7 +242,7 @@ __global__ void __launch_bounds__(256) k_finish(int n, const ImgDesc* __restrict
       atomicAdd(&acc[k], 1ull);
       if (lengths && lengths[img] > 0) atomicAdd(&acc[SDSJ_CTR_BYTES_IN], (unsigned long long)lengths[img]);
       atomicAdd(&acc[SDSJ_CTR_BYTES_OUT], (unsigned long long)(total * (op.out_dtype == SDSJ_DTYPE_F32 ? 4 : 1)));
-      if (lengths && st == SDSJ_OK && d->progressive) atomicAdd(&acc[SDSJ_CTR_PROGRESSIVE], 1ull);
+      if (lengths && st == SDSJ_OK && d->progressive == 1) atomicAdd(&acc[SDSJ_CTR_PROGRESSIVE], 1ull);
       if (lengths && st == SDSJ_OK && d->png) atomicAdd(&acc[SDSJ_CTR_PNG], 1ull);
     }
   }
@@ -334,9 +334,11 @@ int64_t host_plan_frame(ImgDesc* d, int width, int height, const sdsj_op& op) {
 
 // The plan k_parse makes (plan_sample), without k_parse's validation of the Huffman tables: a sample
 // whose tables are bad is sized and routed here like a good one and reported by the device.  It stays
-// that way: sdsj_plan_need / sdsj_plan_need_formats return these statuses and needs.
+// that way: sdsj_plan_need / sdsj_plan_need_formats return these statuses and needs.  A multi-scan
+// sequential file that k_scans refuses while it walks the scans -- after k_plan has given it its scratch -- is
+// such a sample too: status SDSJ_OK and its need here, the refusal (scans_check) in *later.
 int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* status, uint64_t* routes, bool small,
-                       int formats) {
+                       int formats, int* later) {
   ImgDesc d;
   static thread_local ImgTables t;
   MemReader rd{jpg};
@@ -344,6 +346,7 @@ int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* st
   // (the device runs this check in a kernel of its own between k_parse and k_plan: launch_png_meta)
   if (st == SDSJ_OK && d.png && (formats & SDSJ_FORMAT_PNG_META)) st = host_png_meta(jpg, n, d.png_idat_pos, formats);
   *status = st;
+  if (later) *later = st == SDSJ_OK && !d.png && d.progressive == kScansSequential ? scans_check(rd, n, d) : SDSJ_OK;
   if (routes) {
     *routes = kAllRoutes;
     if (st == SDSJ_OK) {

@@ -194,7 +194,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     reaching the parent through HIP IPC); a string = the address of a running service.
 
     ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` /
-    ``"png"`` / ``"png-ext"`` / ``"png-meta"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    ``"jpeg-scans"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
@@ -215,9 +215,16 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     component, mixed ratios -- upsampled as libjpeg does (ratios of 3 and 4 by replication), and RGB-coded files
     (an Adobe marker with transform 0, or component ids ``R`` ``G`` ``B``; Pillow's ``keep_rgb=True``), baseline and
     progressive.  Those images take the unfused colour / resample kernels; every other JPEG decodes exactly as
-    without the name.  CMYK / YCCK, multi-scan sequential, arithmetic and 12-bit files still rerun on PIL.
-    In a served worker process (the decode service) PNG and ``"jpeg-ext"`` samples keep the PIL route whatever this
-    says: the service's wire protocol carries no format mask.
+    without the name.
+    ``"jpeg-scans"`` (it includes ``"jpeg"`` too and combines with ``"jpeg-ext"`` and the PNG names) takes multi-scan
+    sequential files: baseline / extended frames of three components whose components arrive in more than one scan
+    (Y, Cb, Cr one after another, Y then Cb + Cr, any order and grouping; ``jpegtran -scans`` writes them), with
+    restart intervals and with tables redefined between the scans.  One wavefront walks a file's scans, as for
+    progressive files.  A file whose scans are not plain sequential ones, or code a component twice, still reruns
+    on PIL; so do 4:1:1 / RGB-coded multi-scan files unless ``"jpeg-ext"`` is named as well.  Every other JPEG
+    decodes exactly as without the name.  CMYK / YCCK, arithmetic and 12-bit files still rerun on PIL.
+    In a served worker process (the decode service) PNG, ``"jpeg-ext"`` and ``"jpeg-scans"`` samples keep the PIL
+    route whatever this says: the service's wire protocol carries no format mask.
     """
 
     def __init__(self, input_field: str, output_field: Optional[str] = None, resolution=(256, 256),
@@ -264,8 +271,8 @@ class GpuDecodeResizeImageTransform(BaseTransform):
             mask = _lib.format_mask(self.gpu_formats)
             if eng is not None and mask & _lib.FORMAT_PNG and data[:8] == _lib.PNG_SIGNATURE:
                 st, info = _lib.png_probe(data, mask)  # (under the mask: a "png-ext" file is sized natively)
-            elif eng is not None and mask & _lib.FORMAT_JPEG_EXT:
-                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" file is sized natively)
+            elif eng is not None and mask & (_lib.FORMAT_JPEG_EXT | _lib.FORMAT_JPEG_SCANS):
+                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" file is sized natively)
             else:
                 st, info = _lib.probe(data)
             if st != _lib.OK or info.width <= 0 or info.height <= 0:  # not a JPEG this path decodes
@@ -558,7 +565,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"jpeg-ext"``, ``"png"``, ``"png-ext"`` or ``"png-meta"`` to opt in; see
+    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"png"``, ``"png-ext"`` or ``"png-meta"`` to opt in; see
     GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built

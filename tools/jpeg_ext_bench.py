@@ -84,7 +84,7 @@ def make_rgb_pool(count=64, **save):
     return pool
 
 
-def native(pool, n, case):
+def native(pool, n, case, formats=EXT):
     import numpy as np
     import torch
 
@@ -95,19 +95,19 @@ def native(pool, n, case):
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
     blob = torch.from_numpy(np.frombuffer(b"".join(jpgs), np.uint8).copy()).cuda()  # HBM-resident
     d_offs, d_lens = torch.from_numpy(offs).cuda(), torch.tensor(lens, dtype=torch.int32).cuda()
-    need = JpegEngine.scratch_need(pool, RES, formats=EXT) * ((n + len(pool) - 1) // len(pool))
+    need = JpegEngine.scratch_need(pool, RES, formats=formats) * ((n + len(pool) - 1) // len(pool))
     eng = JpegEngine(max_batch=n, scratch_bytes=need + (64 << 20))
-    out, st = eng.decode_resize_device(blob, d_offs, d_lens, RES, formats=EXT)
+    out, st = eng.decode_resize_device(blob, d_offs, d_lens, RES, formats=formats)
     torch.cuda.synchronize()
     assert (st == 0).all(), st[st != 0][:8]
     assert eng.counters()["ok"] == n
     t0 = time.perf_counter()
     for _ in range(3):
-        eng.decode_resize_device(blob, d_offs, d_lens, RES, out=out, status=st, formats=EXT)
+        eng.decode_resize_device(blob, d_offs, d_lens, RES, out=out, status=st, formats=formats)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / 3
     eng.set_timing(True)
-    eng.decode_resize_device(blob, d_offs, d_lens, RES, out=out, status=st, formats=EXT)
+    eng.decode_resize_device(blob, d_offs, d_lens, RES, out=out, status=st, formats=formats)
     stages = {k: round(v, 3) for k, v in eng.stage_times().items() if v > 0.0005}
     eng.set_timing(False)
     folder = tempfile.mkdtemp()
@@ -120,7 +120,7 @@ def native(pool, n, case):
     cpu1 = bench.cpu_baseline(paths, 1, 2.0)
     cpup = bench.cpu_baseline(paths, procs, 4.0)
     return {"route": "native", "case": case,
-            "metric": f"images/s JPEG 640x480 {case} decode+resize@256 (device-resident, gpu_formats jpeg-ext)",
+            "metric": f"images/s JPEG 640x480 {case} decode+resize@256 (device-resident, gpu_formats {formats[-1]})",
             "value": round(n / dt, 1), "batch": n, "calls_timed": 3, "distinct_images": len(pool),
             "mean_jpeg_bytes": round(float(np.mean(lens)), 1), "stage_ms": stages,
             "cpu_baseline": {"value": round(cpup, 1), "cores": procs, "single_core_value": round(cpu1, 1),
@@ -149,7 +149,7 @@ def fallback(pool, n, case):
             "the calling process, resize on the GPU)", "value": round(n / dt, 1), "batch": n}
 
 
-def latency(pool, n, case):
+def latency(pool, n, case, formats=EXT):
     import torch
 
     from sds_amd.presets import create_standard_image_pipeline
@@ -160,7 +160,7 @@ def latency(pool, n, case):
         with open(paths[-1], "wb") as f:
             f.write(j)
     res = {}
-    for name, fm in (("native_ms", EXT), ("default_route_ms", ("jpeg",))):
+    for name, fm in (("native_ms", formats), ("default_route_ms", ("jpeg",))):
         ts = create_standard_image_pipeline("jpg", RES, device="cuda", service=None, gpu_formats=fm)
         for rep in range(2):  # (the first pass warms up)
             torch.cuda.synchronize()
