@@ -4,11 +4,17 @@
 // from the file in argv[1].  The first output line holds kRtUnfused and kRtPng; then one line per record:
 //   status, the 14 plan fields (geo cx0 cy0 cw ch need_h need_v ksh ksv ring_rows fused tile_w rs_fast
 //   rs_lay), the routes (unstuff entropy resample; -9 each unless the status is OK), need (0 unless OK), the
-//   13 off_* fields in plan_image's order, width height ncomp.
+//   13 off_* fields in plan_image's order, width height ncomp, then the entropy / unstuff plan: entropy_len nseg
+//   ntiles sub_bits nsub_cap warm_bits ent_groups lat mh, and warm_small: the warm_bits k_parse gives the image
+//   in a lane of fewer than kWarmSmallLane images (plan_image itself plans for a large lane).
+// `plan_driver --constants` prints instead "name value" lines: the routes, the thresholds the entropy case table
+// reads (tests/entropy_cases.py) and SubState's layout (tests/gpu_debug.py), as the compiler sees them.
 // Each sample is copied into an exactly sized heap buffer, so any read past its end is reported.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <stddef.h>
 
 #include <vector>
 
@@ -16,8 +22,41 @@
 
 using namespace sdsj;
 
+#define SDSJ_PRINT(x) printf(#x " %lld\n", (long long)(x))
+
+static int print_constants() {
+  SDSJ_PRINT(kRtEnt10);
+  SDSJ_PRINT(kRtEnt11);
+  SDSJ_PRINT(kRtEnt11M);
+  SDSJ_PRINT(kRtProg);
+  SDSJ_PRINT(kRtUsSmall);
+  SDSJ_PRINT(kRtUsBig);
+  SDSJ_PRINT(kRtScans);
+  SDSJ_PRINT(kDecodeThreads);
+  SDSJ_PRINT(kMinSubBits);
+  SDSJ_PRINT(kWarmBits);
+  SDSJ_PRINT(kWarmBitsSmall);
+  SDSJ_PRINT(kWarmSmallLane);
+  SDSJ_PRINT(kWarmDiv);
+  SDSJ_PRINT(kSmallBatch);
+  SDSJ_PRINT(kLatSubBits);
+  SDSJ_PRINT(kLatWarm);
+  SDSJ_PRINT(kGroupBits);
+  SDSJ_PRINT(kMaxEntGroups);
+  SDSJ_PRINT(kUsTileBytes);
+  SDSJ_PRINT(kUsSerialTiles);
+  SDSJ_PRINT(kRec);
+  SDSJ_PRINT(sizeof(SubState));
+  SDSJ_PRINT(offsetof(SubState, start_bit));
+  SDSJ_PRINT(offsetof(SubState, end_bit));
+  SDSJ_PRINT(offsetof(SubState, first));
+  SDSJ_PRINT(offsetof(SubState, seg));
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
+  if (!strcmp(argv[1], "--constants")) return print_constants();
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   std::vector<uint8_t> all;
@@ -54,7 +93,9 @@ int main(int argc, char** argv) {
     const int64_t offs[13] = {d->off_ustream, d->off_seg, d->off_tiles,  d->off_sub, d->off_rec, d->off_ptab, d->off_coef,
                               d->off_planes,  d->off_rgb, d->off_tmp,    d->off_kh,  d->off_kv,  d->off_png};
     for (int k = 0; k < 13; k++) printf(" %lld", (long long)offs[k]);
-    printf("  %d %d %d\n", d->width, d->height, d->ncomp);
+    printf("  %d %d %d", d->width, d->height, d->ncomp);
+    printf("  %lld %d %d %d %d %d %d %d %d %d\n", (long long)d->entropy_len, d->nseg, d->ntiles, d->sub_bits, d->nsub_cap,
+           d->warm_bits, d->ent_groups, d->lat, (int)d->mh, d->lat ? d->warm_bits : warm_for(d->sub_bits, kWarmBitsSmall));
     delete d;
     delete t;
     free(buf);

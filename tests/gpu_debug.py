@@ -15,6 +15,7 @@ import sys
 import numpy as np
 
 i32, i64 = ctypes.c_int32, ctypes.c_int64
+u32, u16 = ctypes.c_uint32, ctypes.c_uint16
 
 
 class CompDescC(ctypes.Structure):
@@ -43,6 +44,23 @@ class ImgDescC(ctypes.Structure):
                 ("sm_pad", ctypes.c_int8 * 3), ("etab", i32), ("png_depth_lace", i32),
                 ("png", i32), ("png_ctype", i32), ("png_bpp", i32), ("png_plte_n", i32),
                 ("png_plte_pos", i64), ("png_idat_pos", i64), ("png_raw", i64), ("off_png", i64)]
+
+
+class SubStateC(ctypes.Structure):
+    """sdsj::SubState (scratch at off_sub, one per subsequence); tests/test_entropy_cases_table.py pins its size
+    and the offsets of the fields read here to the compiler's."""
+    _fields_ = [(n, u32) for n in ("start_bit", "end_bit", "entry_p", "cur_exit_p", "spec_exit_p", "new_exit_p",
+                                   "new_entry_p", "res_p")] + \
+               [(n, u16) for n in ("entry_bz", "cur_exit_bz", "spec_exit_bz", "new_exit_bz", "new_entry_bz", "res_bz")] + \
+               [(n, i32) for n in ("cur_nblk", "spec_nblk", "new_nblk", "nrec", "res_nblk", "res_ri")] + \
+               [(n, i32 * 3) for n in ("cur_dc", "spec_dc", "new_dc", "res_dc", "res_q")] + \
+               [("nblk_ex", i32), ("dc_ex", i32 * 3), ("first", i32), ("seg", i32), ("lim_bit", u32), ("pad", i32)]
+
+
+def sub_states(d, fetch) -> np.ndarray:
+    """The image's nsub SubState records as a structured array (fields as SubStateC)."""
+    raw = fetch(d.off_sub, d.nsub * ctypes.sizeof(SubStateC))
+    return np.frombuffer(raw.tobytes(), dtype=np.dtype(SubStateC))
 
 
 def _memcpy_d2h(ptr: int, nbytes: int) -> np.ndarray:

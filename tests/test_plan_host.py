@@ -35,42 +35,47 @@ OFFSETS = ("off_ustream", "off_seg", "off_tiles", "off_sub", "off_rec", "off_pta
            "off_tmp", "off_kh", "off_kv", "off_png")  # plan_image's take order
 LAYOUT_OPS = (P.Op(256, 256, True, "bilinear"), P.Op(512, 512, False, "bicubic"), P.Op(48, 64, True, "lanczos"),
               P.Op(100, 100, True, "nearest"))
+# (warm_bits: plan_image's, for a lane of at least kWarmSmallLane images; warm_small: what k_parse gives below it)
+ENT_FIELDS = ("entropy_len", "nseg", "ntiles", "sub_bits", "nsub_cap", "warm_bits", "ent_groups", "lat", "mh",
+              "warm_small")  # the entropy / unstuff plan (tests/test_entropy_cases_table.py)
 DAMAGE_OP = P.Op(256, 256, True, "bilinear")
 
 
 class Row:
     def __init__(self, line: str):
         v = list(map(int, line.split()))
-        assert len(v) == 1 + len(PLAN_FIELDS) + 3 + 1 + len(OFFSETS) + 3, line
+        assert len(v) == 1 + len(PLAN_FIELDS) + 3 + 1 + len(OFFSETS) + 3 + len(ENT_FIELDS), line
         self.status = v[0]
         self.plan = dict(zip(PLAN_FIELDS, v[1:15]))
         self.routes = tuple(v[15:18])  # unstuffing, entropy, resample
         self.need = v[18]
         self.offsets = v[19:32]
         self.size = tuple(v[32:35])    # width, height, ncomp
+        self.ent = dict(zip(ENT_FIELDS, v[35:45]))
 
 
 def record(op: P.Op, small: int, formats: int, data: bytes) -> bytes:
     return struct.pack("<6iI", op.out_h, op.out_w, int(op.crop), FILTERS[op.filter], small, formats, len(data)) + data
 
 
-@pytest.fixture(scope="module")
-def run():
-    """Builds the driver once; run(records) plans them all in one process and returns their rows."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
+def build_driver(sanitize: bool = True):
+    """Builds the driver; the returned run(records) plans them all in one process and returns their rows, and
+    run.constants() returns what `plan_driver --constants` prints, {name: value}.  sanitize=False: the same
+    program without the sanitizers, for callers that only need the rows (the GPU tests)."""
     d = tempfile.mkdtemp()
     exe = os.path.join(d, "plan_driver")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-I", os.path.join(HERE, "..", "include"), DRIVER, "-o", exe],
+    flags = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    r = subprocess.run(["g++", "-std=c++17", "-O1", *flags, "-I", os.path.join(HERE, "..", "include"), DRIVER, "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ)
+    if sanitize:
+        env.update(ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
 
     def go(records):
         blob = os.path.join(d, "inputs.bin")
         with open(blob, "wb") as f:
             f.write(b"".join(records))
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
         r = subprocess.run([exe, blob], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, r.stderr[-4000:]
         assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
@@ -78,7 +83,21 @@ def run():
         assert tuple(map(int, lines[0].split())) == (P.RT_UNFUSED, RT_PNG)
         assert len(lines) == 1 + len(records)
         return [Row(l) for l in lines[1:]]
+
+    def constants():
+        r = subprocess.run([exe, "--constants"], capture_output=True, text=True, env=env, timeout=60)
+        assert r.returncode == 0 and "runtime error" not in r.stderr, r.stderr[-4000:]
+        return {k: int(v) for k, v in (l.rsplit(None, 1) for l in r.stdout.splitlines())}
+    go.constants = constants
     return go
+
+
+@pytest.fixture(scope="module")
+def run():
+    """Builds the sanitized driver once."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    return build_driver()
 
 
 def test_restated_planner_equals_plan_image(run):
