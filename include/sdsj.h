@@ -256,6 +256,26 @@ int sdsj_resize_frames_device(sdsj_engine* eng, int n, const uint8_t* d_frames, 
 int sdsj_engine_counters(sdsj_engine* eng, uint64_t* out, int cap, int reset);
 const char* sdsj_counter_name(int k);
 
+/* Entry-point store.  The device-resident entry point keeps, per row it has decoded -- keyed by the sample's
+ * device address --, the entry state of every entropy subsequence, and on a later call over the same bytes
+ * skips the speculative and sync passes that compute them: a dataset resident in device memory is decoded
+ * epoch after epoch.  The write pass proves every stored state while it decodes and falls back to the full
+ * decode in the same call, so a sample replaced in place costs time and never pixels.  It serves baseline images
+ * of the single-workgroup 11-bit route; the host entry points never use it.
+ * sdsj_engine_set_hints: rows the store holds (default 2 x max_batch, about 4.2 KB of device memory each,
+ * allocated on the first device-resident call; 0 turns the store off, as the environment's SDSJ_HINTS=0 does);
+ * waits for the device, and empties the store.  sdsj_engine_clear_hints empties it.
+ * sdsj_engine_hint_counters: as sdsj_engine_counters, for the store's own counters (SDSJ_HINT_CTR_*). */
+#define SDSJ_HINT_CTR_HITS 0          /* images decoded from stored entry states, proved by the write pass */
+#define SDSJ_HINT_CTR_MISSES 1        /* eligible images without a usable record */
+#define SDSJ_HINT_CTR_VERIFY_FAILED 2 /* images whose record the write pass refuted (decoded again in the call) */
+#define SDSJ_HINT_CTR_STORED 3        /* records written */
+#define SDSJ_NUM_HINT_COUNTERS 4
+int sdsj_engine_set_hints(sdsj_engine* eng, int64_t rows);
+int sdsj_engine_clear_hints(sdsj_engine* eng);
+int sdsj_engine_hint_counters(sdsj_engine* eng, uint64_t* out, int cap, int reset);
+const char* sdsj_hint_counter_name(int k);
+
 /* Kernel lanes: a batch of >= 256 x L images runs as L contiguous lanes on L streams whose kernel
  * sequences overlap (default 4, at most 4).  1 = one dispatch of every kernel per batch, the setting
  * under which a kernel's launch duration is measured alone (bench.py roofline). */

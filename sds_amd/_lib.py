@@ -34,9 +34,11 @@ EXPORTS = [
     "sdsj_stage_name", "sdsj_engine_debug_buffers", "sdsj_resize_frames_device", "sdsj_submit_batch",
     "sdsj_submit_files", "sdsj_wait_batch", "sdsj_engine_counters", "sdsj_counter_name", "sdsj_engine_set_lanes",
     "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve", "sdsj_engine_set_formats", "sdsj_png_probe",
-    "sdsj_plan_need_formats", "sdsj_png_probe_formats", "sdsj_probe_formats",
+    "sdsj_plan_need_formats", "sdsj_png_probe_formats", "sdsj_probe_formats", "sdsj_engine_set_hints",
+    "sdsj_engine_clear_hints", "sdsj_engine_hint_counters", "sdsj_hint_counter_name",
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
+NUM_HINT_COUNTERS = 4  # SDSJ_NUM_HINT_COUNTERS (the entry-point store's: sdsj_engine_hint_counters)
 FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META, FORMAT_JPEG_EXT = 1, 2, 4, 16, 64  # SDSJ_FORMAT_*
 FORMAT_JPEG_SCANS = 128
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
@@ -152,6 +154,11 @@ def load() -> ctypes.CDLL:
         lib.sdsj_counter_name.argtypes = [ctypes.c_int]
         lib.sdsj_counter_name.restype = ctypes.c_char_p
         lib.sdsj_engine_set_lanes.argtypes = [vp, ctypes.c_int]
+        lib.sdsj_engine_set_hints.argtypes = [vp, i64]
+        lib.sdsj_engine_clear_hints.argtypes = [vp]
+        lib.sdsj_engine_hint_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int, ctypes.c_int]
+        lib.sdsj_hint_counter_name.argtypes = [ctypes.c_int]
+        lib.sdsj_hint_counter_name.restype = ctypes.c_char_p
         lib.sdsj_engine_reserve.argtypes = [vp, i64]
         lib.sdsj_plan_need.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjOp), ctypes.POINTER(i64)]
         lib.sdsj_service_serve.argtypes = [ctypes.POINTER(SdsjServiceCfg)]

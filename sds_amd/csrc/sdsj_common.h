@@ -223,7 +223,13 @@ struct ImgDesc {
   int32_t smooth, sm_good;
   int8_t sm_bits[2][kMaxComp][10];
   int8_t mh;  // latency mode: the multi-hypothesis speculative pass (k_entspec_mh) takes the image
-  int8_t sm_pad[3];
+  union {
+    int8_t sm_pad[3];
+    // entry-point store (HintHdr below), in the first pad byte (the struct's size and offsets are pinned):
+    // kHintHit = k_enthint filled the SubStates from a record, kHintFailed = k_entwrite's verification
+    // refused them (the image goes to the retry list)
+    int8_t hinted;
+  };
   int32_t etab;  // k_enttab: the image whose EntTables it decodes with (itself, or image 0 of the lane when equal)
   int32_t png_depth_lace;  // PNG samples: IHDR's bit depth | interlace method << 8 (png_fill_desc); otherwise unused
   // PNG sample (sdsj_png.h png_parse; engines with SDSJ_FORMAT_PNG enabled): no components or entropy
@@ -287,6 +293,48 @@ struct alignas(8) SyncRec {
   uint8_t blk;      // MCU block index of the completed block
   uint8_t pad;
 };
+
+// Entry-point store: per row of the device-resident path, what k_entspec and k_entsync
+// compute for k_entwrite -- every subsequence's verified entry state -- kept by the engine from call to
+// call, keyed by the sample's device address.  A record is a header (what the subsequence layout depends
+// on, compared on lookup; the two sync statistics the descriptor reports) and one packed entry per
+// subsequence of the single-group layout: x = entry bit, y = MCU block << 24 | exclusive block count,
+// z = DC sum 0 | DC sum 1 << 16, w = DC sum 2 (16 bits each; a row whose values do not fit is not kept).
+// k_entwrite proves a record right while it decodes (every lane's exit against its successor's entry),
+// so a stale or torn record costs a second decode and never a coefficient.
+constexpr int8_t kHintHit = 1, kHintFailed = 2;
+struct HintHdr {
+  uint64_t key;  // the sample's device address
+  int32_t length, nsub;
+  int64_t entropy_len, ulen;
+  int32_t sub_bits, nseg, bpm, sync_rounds, pad0;
+  int32_t pad[3];
+};
+static_assert(sizeof(HintHdr) == 64, "a record's entries stay 16-byte aligned");
+constexpr int kHintRowBytes = (int)sizeof(HintHdr) + 16 * kDecodeThreads;
+constexpr int kHintProbes = 128;  // linear probes before a row goes unrecorded
+// Open addressing over 2 x rows key slots (at most half full: probe runs stay short), each naming its record: the
+// first `rows` keys to arrive take the records in arrival order (*count), later ones hold a slot without one.
+struct HintStore {
+  unsigned long long* keys;  // [2 * rows], 0 = free
+  int32_t* ridx;             // [2 * rows] record + 1 of the slot's key, 0 = none (yet)
+  int32_t* count;            // records handed out (may pass rows: the surplus got none)
+  uint8_t* recs;             // record r at recs + r * kHintRowBytes
+  int64_t rows;
+};
+SDSJ_HD inline uint64_t hint_hash(uint64_t key) {
+  key ^= key >> 33;
+  key *= 0xff51afd7ed558ccdull;
+  key ^= key >> 33;
+  return key;
+}
+// Per-lane work lists of the store (int32): two blocks of kHintListHdr + cap entries, [0] = the count --
+// the route's images k_enthint left to the speculative and sync passes, then the images whose records
+// failed k_entwrite's verification.
+constexpr int kHintListHdr = 16;
+SDSJ_HD inline int64_t hint_lane_ints(int cap) { return 2 * ((int64_t)kHintListHdr + cap); }
+SDSJ_HD inline int32_t* hint_retry_list(int32_t* lane, int cap) { return lane + kHintListHdr + cap; }
+constexpr int kRtHintMiss = 62;      // bit of a route hint (no route): the speculative pass had images last time
 
 // Restart-interval table (scratch at off_seg).  Interval k = the k-th restart interval (the whole
 // scan without DRI).  k_unstuff fills [lo[k], hi[k]) = the unstuffed bytes it decodes, chosen the way

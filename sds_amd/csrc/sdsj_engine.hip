@@ -100,7 +100,7 @@ struct sdsj_engine {
   uint64_t hint_key[kHintSlots] = {};
   uint64_t hint[kHintSlots] = {};
   int hint_n = 0, hint_next = 0;
-  PinnedBuf<int32_t> h_rcounts;  // [kMaxLanes][kNumRoutes]
+  PinnedBuf<int32_t> h_rcounts;  // [kMaxLanes][kNumRoutes], then [kMaxLanes]: the lanes' k_enthint miss counts
   Event ev_rc[kMaxLanes];
   bool rc_pending = false;
   int rc_lanes = 0;
@@ -110,6 +110,14 @@ struct sdsj_engine {
   PinnedBuf<int32_t> h_froutes;
   DeviceBuf<float> d_lut;
   DeviceBuf<unsigned long long> d_counters;  // SDSJ_CTR_* (k_finish)
+  // entry-point store of the device path (sdsj_common.h HintHdr): hint_rows slots of a key and a record,
+  // allocated by the first device-resident call; per-lane work lists; SDSJ_HINT_CTR_*
+  int64_t hint_rows = -1;  // < 0: 2 x max_batch
+  DeviceBuf<unsigned long long> d_hint_keys;  // [2 x hint_rows]
+  DeviceBuf<int32_t> d_hint_ridx;             // [2 x hint_rows], then the record count
+  DeviceBuf<uint8_t> d_hint_recs;
+  DeviceBuf<int32_t> d_hint_lanes;  // [kMaxLanes][hint_lane_ints(max_batch)]
+  DeviceBuf<unsigned long long> d_hint_ctr;
   // host paths: sdsj_decode_resize_batch stages each chunk in `sync_stage`, sdsj_submit_* in slots[slot] with
   // the H2D copy on copy_stream; parallel_for's persistent threads are created on first use
   Staging sync_stage, slots[SDSJ_SLOTS];
@@ -197,7 +205,8 @@ struct Lane {
 // engine's pinned readback slot rc_lane after k_plan
 int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d_blob, int64_t blob_bytes, const int64_t* d_offsets,
              const int32_t* d_lengths, const sdsj_op& op, const uint8_t* d_flip, void* d_out, int32_t* d_status,
-             hipStream_t s, hipEvent_t after_spec, uint64_t rm, uint64_t hint = kAllRoutes, int rc_lane = -1) {
+             hipStream_t s, hipEvent_t after_spec, uint64_t rm, uint64_t hint = kAllRoutes, int rc_lane = -1,
+             const HintLane* hl = nullptr) {
   std::vector<Event>* evs = nullptr;
   if (e->timing) {
     if (e->ev_used == e->ev_sets.size()) {
@@ -222,6 +231,9 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   if (rc_lane >= 0) {
     SDSJ_HIP(e, hipMemcpyAsync(e->h_rcounts.get() + rc_lane * kNumRoutes, ln.routes, sizeof(int32_t) * kNumRoutes,
                                hipMemcpyDeviceToHost, s));
+    if (hl)  // (what k_enthint left the speculative pass in this lane's previous call: its list is reset below)
+      SDSJ_HIP(e, hipMemcpyAsync(e->h_rcounts.get() + kMaxLanes * kNumRoutes + rc_lane, hl->lane, sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, s));
     SDSJ_HIP(e, hipEventRecord(e->ev_rc[rc_lane].get(), s));
   }
   mark(2);
@@ -239,11 +251,11 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   else if (evs)
     (void)hipEventRecord((*evs)[kPngEvent + 1].get(), s);
   mark(4);
-  SDSJ_HIP(e, launch_entspec(n, ln.descs, ln.tables, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, small, hint));
+  SDSJ_HIP(e, launch_entspec(n, ln.descs, ln.tables, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, small, hint, hl));
   mark(5);
-  SDSJ_HIP(e, launch_entsync(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint));
+  SDSJ_HIP(e, launch_entsync(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint, hl));
   mark(6);
-  SDSJ_HIP(e, launch_entwrite(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint, small));
+  SDSJ_HIP(e, launch_entwrite(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint, small, hl));
   mark(7);
   SDSJ_HIP(e, launch_idct(n, ln.descs, ln.tables, e->scratch.get(), s));
   mark(8);
@@ -297,7 +309,7 @@ void hint_store(sdsj_engine* e, uint64_t key, uint64_t h) {
 // host-planned in latency mode (host paths, n <= kSmallBatch)
 int run_chunk(sdsj_engine* e, int n, const uint8_t* d_blob, int64_t blob_bytes, const int64_t* d_offsets, const int32_t* d_lengths,
               const sdsj_op& op, const uint8_t* d_flip, void* d_out, int32_t* d_status, hipStream_t s,
-              uint64_t rm = kAllRoutes, bool small = false) {
+              uint64_t rm = kAllRoutes, bool small = false, bool hints = false) {
   int nl = std::min(std::max(e->lanes, 1), kMaxLanes);
   while (nl > 1 && n < nl * kLaneMin) nl--;
   // route hint: the host paths know their routes exactly (rm); the device path uses the routes that held
@@ -324,6 +336,8 @@ int run_chunk(sdsj_engine* e, int n, const uint8_t* d_blob, int64_t blob_bytes, 
           for (int r = 0; r < kNumRoutes; r++)
             if (e->h_rcounts.get()[k * kNumRoutes + r] > 0) h |= 1ull << r;
         if (h & (1ull << kRtEnt11M)) h |= 1ull << kRtEnt11G;
+        for (int k = 0; k < e->rc_lanes; k++)  // (with the store off the bit is never read)
+          if (e->h_rcounts.get()[kMaxLanes * kNumRoutes + k] != 0) h |= 1ull << kRtHintMiss;
         hint_store(e, e->rc_key, h);
         e->rc_pending = false;
       }
@@ -338,9 +352,19 @@ int run_chunk(sdsj_engine* e, int n, const uint8_t* d_blob, int64_t blob_bytes, 
     e->rc_lanes = lanes;
     e->rc_key = key;
   };
+  // the entry-point store serves the device path's throughput plan (the host paths' staging addresses mean nothing)
+  hints = hints && !small && e->d_hint_keys;
+  const size_t hli = (size_t)hint_lane_ints(e->max_batch);
+  auto hint_lane = [&](int k, int i0) {
+    return HintLane{HintStore{e->d_hint_keys.get(), e->d_hint_ridx.get(), e->d_hint_ridx.get() + 2 * e->hint_rows,
+                              e->d_hint_recs.get(), e->hint_rows},
+                    e->d_hint_lanes.get() + k * hli,
+                    e->d_hint_ctr.get(), d_blob, d_offsets + i0, d_lengths + i0};
+  };
   if (nl == 1) {
+    const HintLane hl = hint_lane(0, 0);
     const int st = run_lane(e, first, n, small, d_blob, blob_bytes, d_offsets, d_lengths, op, d_flip, d_out, d_status, s,
-                            nullptr, rm, hint, readback ? 0 : -1);
+                            nullptr, rm, hint, readback ? 0 : -1, hints ? &hl : nullptr);
     if (st == SDSJ_OK) readback_queued(1);
     return st;
   }
@@ -361,9 +385,10 @@ int run_chunk(sdsj_engine* e, int n, const uint8_t* d_blob, int64_t blob_bytes, 
                                   k == 1 ? e->d_total.get() : e->d_totals_x.get() + (k - 2)};
     hipStream_t ls = k == 0 ? s : e->aux[k - 1].get();
     if (k > 0) SDSJ_HIP(e, hipStreamWaitEvent(ls, e->ev_mid[k - 1].get(), 0));
+    const HintLane hl = hint_lane(k, i0);
     int st = run_lane(e, ln, i1 - i0, small, d_blob, blob_bytes, d_offsets + i0, d_lengths + i0, op, d_flip ? d_flip + i0 : nullptr,
                       static_cast<uint8_t*>(d_out) + i0 * ob, d_status + i0, ls,
-                      k + 1 < nl ? e->ev_mid[k].get() : nullptr, rm, hint, readback ? k : -1);
+                      k + 1 < nl ? e->ev_mid[k].get() : nullptr, rm, hint, readback ? k : -1, hints ? &hl : nullptr);
     if (st != SDSJ_OK) return st;
   }
   readback_queued(nl);
@@ -562,9 +587,14 @@ int engine_init(sdsj_engine* e, const sdsj_cfg* cfg) {
   const size_t mb = (size_t)e->max_batch, routes = (size_t)route_ints(e->max_batch);
   if (!e->descs.reserve(mb) || !e->tables.reserve(mb) || !e->d_total.reserve(1) || !e->d_totals_x.reserve(kMaxLanes - 1) ||
       !e->d_routes_x.reserve((kMaxLanes - 1) * routes) || !e->d_etab.reserve(enttab_bytes() * mb) ||
-      !e->d_routes.reserve(routes) || !e->d_lut.reserve(256) || !e->h_rcounts.reserve(kMaxLanes * kNumRoutes) ||
-      !e->d_counters.reserve(SDSJ_NUM_COUNTERS))
+      !e->d_routes.reserve(routes) || !e->d_lut.reserve(256) || !e->h_rcounts.reserve(kMaxLanes * (kNumRoutes + 1)) ||
+      !e->d_counters.reserve(SDSJ_NUM_COUNTERS) || !e->d_hint_ctr.reserve(SDSJ_NUM_HINT_COUNTERS))
     return SDSJ_ENOMEM;
+  if (const char* h = getenv("SDSJ_HINTS"))
+    if (atoi(h) == 0) e->hint_rows = 0;
+  if (e->hint_rows < 0) e->hint_rows = 2 * (int64_t)e->max_batch;
+  for (int k = 0; k < kMaxLanes * (kNumRoutes + 1); k++) e->h_rcounts.get()[k] = 0;
+  if (hipMemset(e->d_hint_ctr.get(), 0, sizeof(unsigned long long) * SDSJ_NUM_HINT_COUNTERS) != hipSuccess) return SDSJ_EHIP;
   for (auto& ev : e->ev_rc)
     if (hipEventCreateWithFlags(ev.put(), hipEventDisableTiming) != hipSuccess) return SDSJ_EHIP;
   if (hipMemset(e->d_counters.get(), 0, sizeof(unsigned long long) * SDSJ_NUM_COUNTERS) != hipSuccess) return SDSJ_EHIP;
@@ -581,6 +611,38 @@ int engine_init(sdsj_engine* e, const sdsj_cfg* cfg) {
     return ensure_scratch(e, cfg->scratch_bytes);
   }
   return SDSJ_OK;
+}
+
+// Every key slot free, no record handed out.  (The caller has waited for the device.)
+int hints_empty(sdsj_engine* e) {
+  const size_t slots = 2 * (size_t)e->hint_rows;
+  SDSJ_HIP(e, hipMemset(e->d_hint_keys.get(), 0, sizeof(unsigned long long) * slots));
+  SDSJ_HIP(e, hipMemset(e->d_hint_ridx.get(), 0, sizeof(int32_t) * (slots + 1)));
+  return SDSJ_OK;
+}
+
+// The entry-point store's memory, on the first device-resident call that may use it.  A store that cannot be
+// allocated is a store turned off: the call decodes the ordinary way.
+int ensure_hints(sdsj_engine* e) {
+  if (e->hint_rows <= 0 || e->d_hint_keys) return SDSJ_OK;
+  const size_t lanes = (size_t)kMaxLanes * (size_t)hint_lane_ints(e->max_batch);
+  const size_t slots = 2 * (size_t)e->hint_rows;
+  if (!e->d_hint_recs.reserve((size_t)e->hint_rows * kHintRowBytes) || !e->d_hint_lanes.reserve(lanes) ||
+      !e->d_hint_ridx.reserve(slots + 1) || !e->d_hint_keys.reserve(slots)) {
+    (void)hipGetLastError();
+    e->d_hint_keys.reset();
+    e->d_hint_ridx.reset();
+    e->d_hint_recs.reset();
+    e->hint_rows = 0;
+    return SDSJ_OK;
+  }
+  SDSJ_HIP(e, hipMemset(e->d_hint_lanes.get(), 0, sizeof(int32_t) * lanes));
+  return hints_empty(e);
+}
+
+// An emptied store (or another size) makes every row a miss: the speculative pass gets its full grid again.
+void hints_forget(sdsj_engine* e) {
+  for (int k = 0; k < e->hint_n; k++) e->hint[k] |= 1ull << kRtHintMiss;
 }
 }  // namespace
 
@@ -740,11 +802,15 @@ int sdsj_decode_resize_batch_device(sdsj_engine* e, int n, const uint8_t* d_blob
     int st = ensure_scratch(e, (int64_t)2 << 30);
     if (st != SDSJ_OK) return st;
   }
+  {
+    const int st = ensure_hints(e);
+    if (st != SDSJ_OK) return st;
+  }
   const int64_t ob = out_bytes_per_image(*op);
   for (int c0 = 0; c0 < n; c0 += e->max_batch) {
     int m = std::min(e->max_batch, n - c0);
     int st = run_chunk(e, m, d_blob, (int64_t)blob_bytes, d_offsets + c0, d_lengths + c0, *op, d_flip ? d_flip + c0 : nullptr,
-                       reinterpret_cast<uint8_t*>(d_out) + c0 * ob, d_status + c0, s);
+                       reinterpret_cast<uint8_t*>(d_out) + c0 * ob, d_status + c0, s, kAllRoutes, false, true);
     if (st != SDSJ_OK) return st;
   }
   return SDSJ_OK;
@@ -897,6 +963,44 @@ const char* sdsj_counter_name(int k) {
                                                  "other",     "bytes_in",  "bytes_out",   "frames",  "progressive",
                                                  "png"};
   return k >= 0 && k < SDSJ_NUM_COUNTERS ? names[k] : "";
+}
+
+int sdsj_engine_set_hints(sdsj_engine* e, int64_t rows) {
+  if (!e || rows < 0) return SDSJ_EINVAL;
+  DeviceGuard g(e->device);
+  SDSJ_HIP(e, hipDeviceSynchronize());
+  e->d_hint_keys.reset();
+  e->d_hint_ridx.reset();
+  e->d_hint_recs.reset();
+  e->hint_rows = rows;  // (allocated by the next device-resident call)
+  hints_forget(e);
+  return SDSJ_OK;
+}
+
+int sdsj_engine_clear_hints(sdsj_engine* e) {
+  if (!e) return SDSJ_EINVAL;
+  if (!e->d_hint_keys) return SDSJ_OK;
+  DeviceGuard g(e->device);
+  SDSJ_HIP(e, hipDeviceSynchronize());
+  const int st = hints_empty(e);
+  hints_forget(e);
+  return st;
+}
+
+int sdsj_engine_hint_counters(sdsj_engine* e, uint64_t* out, int cap, int reset) {
+  if (!e || (cap > 0 && !out)) return SDSJ_EINVAL;
+  DeviceGuard g(e->device);
+  unsigned long long h[SDSJ_NUM_HINT_COUNTERS];
+  SDSJ_HIP(e, hipDeviceSynchronize());
+  SDSJ_HIP(e, hipMemcpy(h, e->d_hint_ctr.get(), sizeof(h), hipMemcpyDeviceToHost));
+  for (int k = 0; k < cap && k < SDSJ_NUM_HINT_COUNTERS; k++) out[k] = (uint64_t)h[k];
+  if (reset) SDSJ_HIP(e, hipMemset(e->d_hint_ctr.get(), 0, sizeof(h)));
+  return SDSJ_OK;
+}
+
+const char* sdsj_hint_counter_name(int k) {
+  static const char* names[SDSJ_NUM_HINT_COUNTERS] = {"hint_hits", "hint_misses", "hint_verify_failed", "hint_stored"};
+  return k >= 0 && k < SDSJ_NUM_HINT_COUNTERS ? names[k] : "";
 }
 
 int sdsj_engine_set_lanes(sdsj_engine* e, int lanes) {

@@ -1000,6 +1000,44 @@ __device__ int sync_full(const TT& T, const BlkCtx& K, const uint32_t* src, SubS
   return nsym;
 }
 
+// The subsequence layout of an image: restart interval s (bytes [lo[s], hi[s])) -> max(1, ceil(bits /
+// sub_bits)) subsequences, in interval order; fills start_bit, end_bit, first, seg and lim_bit of each and
+// returns their number (at most nsub_cap).  Every thread of the NT-thread workgroup calls it; tmp: NT ints of LDS.
+template <int NT>
+__device__ __forceinline__ int ent_layout(const ImgDesc* d, const SegView& sv, SubState* sub, int32_t* tmp) {
+  const int t = threadIdx.x, nseg = d->nseg;
+  const uint32_t SB = (uint32_t)d->sub_bits;
+  int carry = 0;
+  for (int base = 0; base < nseg; base += NT) {
+    const int s = base + t;
+    int cnt = 0;
+    uint32_t b0 = 0, b1 = 0;
+    if (s < nseg) {
+      b0 = (uint32_t)sv.lo[s] * 8u;
+      b1 = (uint32_t)sv.hi[s] * 8u;
+      if (b1 < b0) b1 = b0;
+      cnt = b1 > b0 ? (int)((b1 - b0 + SB - 1) / SB) : 1;
+    }
+    int total;
+    const int off = carry + block_excl_scan<NT>(cnt, tmp, &total);
+    if (s < nseg) {
+      for (int k = 0; k < cnt; k++) {
+        const int j = off + k;
+        if (j >= d->nsub_cap) break;
+        SubState& S = sub[j];
+        S.start_bit = b0 + (uint32_t)k * SB;
+        const uint32_t e = S.start_bit + SB;
+        S.end_bit = e < b1 ? e : b1;
+        S.first = k == 0;
+        S.seg = s;
+        S.lim_bit = b1;
+      }
+    }
+    carry += total;
+  }
+  return carry < d->nsub_cap ? carry : d->nsub_cap;
+}
+
 // The speculative pass's LDS: tables, the layout scan's scratch, statistics -- not the sync kernel's
 // task / scan arrays (5 KB that cost it two workgroups per CU)
 template <int LB, int NT>
@@ -1035,40 +1073,10 @@ __device__ void entspec_image(int img, int grp, ImgDesc* __restrict__ descs, con
   const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
   SubState* sub = reinterpret_cast<SubState*>(scratch + d->off_sub);
   SyncRec* recs = reinterpret_cast<SyncRec*>(scratch + d->off_rec);
-  const int nseg = d->nseg;
-  const uint32_t SB = (uint32_t)d->sub_bits;
 
-  // --- subsequence layout: restart interval s (bytes [lo[s], hi[s])) -> max(1, ceil(bits / SB)) ---
   {
-    int carry = 0;
-    for (int base = 0; base < nseg; base += NT) {
-      const int s = base + t;
-      int cnt = 0;
-      uint32_t b0 = 0, b1 = 0;
-      if (s < nseg) {
-        b0 = (uint32_t)sv.lo[s] * 8u;
-        b1 = (uint32_t)sv.hi[s] * 8u;
-        if (b1 < b0) b1 = b0;
-        cnt = b1 > b0 ? (int)((b1 - b0 + SB - 1) / SB) : 1;
-      }
-      int total;
-      const int off = carry + block_excl_scan<NT>(cnt, L.tmp, &total);
-      if (s < nseg) {
-        for (int k = 0; k < cnt; k++) {
-          const int j = off + k;
-          if (j >= d->nsub_cap) break;
-          SubState& S = sub[j];
-          S.start_bit = b0 + (uint32_t)k * SB;
-          const uint32_t e = S.start_bit + SB;
-          S.end_bit = e < b1 ? e : b1;
-          S.first = k == 0;
-          S.seg = s;
-          S.lim_bit = b1;
-        }
-      }
-      carry += total;
-    }
-    if (t == 0) L.nsub = carry < d->nsub_cap ? carry : d->nsub_cap;
+    const int cnt = ent_layout<NT>(d, sv, sub, L.tmp);
+    if (t == 0) L.nsub = cnt;
   }
   __syncthreads();
   const int nsub = L.nsub;
@@ -1366,6 +1374,26 @@ __device__ int load_write_tables(WriteTables& W, const EntTables* g, int32_t* tm
   return ns;
 }
 
+// The write pass's proof of a stored entry state (entwrite_image, LB = 11): a lane that stopped at bit `pos`, MCU
+// block blk, after nblk blocks of its interval (which holds seg_blocks), with the rotated predictors (pc: the next
+// block's component, p0 / p1: the following ones in the MCU's component cycle; pk_c: BlkCtx::pc), against its
+// successor's entry N.  Out of line: inside the pass it cost the decode loop 8 VGPRs and a wave of occupancy.
+__device__ __attribute__((noinline)) bool entry_proved(const SubState& N, uint32_t pos, int blk, int nblk, int seg_blocks,
+                                                       int pc, int p0, int p1, int ncomp, uint32_t pk_c, int bpm) {
+  // (a lane that ran out of blocks stopped early, as the sync pass's did not: then every later lane of the
+  // interval must start out of blocks too, and none of them stores anything)
+  if (nblk >= seg_blocks) return N.nblk_ex >= seg_blocks;
+  auto comp = [&](int bk) { return (int)(pk_c >> (2 * bk)) & 3; };
+  int succ[kMaxComp] = {0, 0, 0};
+  for (int bb = 0; bb < bpm; bb++) {
+    const int cb = comp(bb), cn = comp(bb + 1 == bpm ? 0 : bb + 1);
+    if (cn != cb) succ[cb] = cn;
+  }
+  const int ce = comp(blk), c1 = succ[ce], c2 = succ[c1];
+  return pos == N.entry_p && (uint32_t)blk == (uint32_t)(N.entry_bz >> 8) && nblk == N.nblk_ex && pc == N.dc_ex[ce] &&
+         (ncomp != 3 || (p0 == N.dc_ex[c1] && p1 == N.dc_ex[c2]));
+}
+
 // CP: the variant that writes the compact coefficient format (sdsj_common.h coef_compact: LB = 11 images
 // outside latency mode); each variant skips the other's images.  A lane's images are all in latency mode or
 // none is (k_parse's `small`), so launch_entwrite launches one of the two.
@@ -1410,6 +1438,9 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
   const int my_base = t * kStride;
   int bad = 0;
   unsigned long long nsym = 0, witers = 0;
+  // entry states from the store (k_enthint), proved below.  Only the compact variant meets them: the int16 one
+  // decodes latency-mode lanes, which the store never serves, and stays the code it was
+  const bool hinted = CP && d->hinted == kHintHit;
 
   const int G = d->ent_groups, per = (nsub + G - 1) / G, j0 = grp * per, j1 = j0 + per < nsub ? j0 + per : nsub;
   for (int jb = j0; jb < j1; jb += kEntThreads) {  // uniform trip count for the whole workgroup
@@ -1607,6 +1638,21 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
       if (g < gend) sv.vend[s_int] = g;                     // the rest of the interval stays zero
       if (b.pos > lim) sv.flag[s_int] |= kSegIns;          // ran out of data (JWRN_HIT_MARKER)
     }
+    if constexpr (CP) {
+      // Entries from the store are proved here: this lane entered at sub[j].entry and stopped by the rule the
+      // speculative and sync passes use, so its exit is its successor's entry when its own entry was right.
+      // An interval's first entry is exact by the layout; if every lane's exit equals the next entry -- bit
+      // position, MCU block, block count, predictors -- every entry is the sequential decoder's by induction.
+      if (hinted && active && !last_of_seg) {
+        // (the successor's address and the interval's first block from values the compiler cannot tell from the
+        // ones before the loop: kept across it, they cost the decode loop registers and a wave of occupancy)
+        int jn = j + 1, g0 = s_int;
+        asm volatile("" : "+v"(jn), "+v"(g0));
+        g0 *= blocks_per_seg;
+        const bool ok = entry_proved(sub[jn], b.pos, blk, g - g0, gend - g0, pc, p0, p1, ncomp, K.pc, K.bpm);
+        if (!ok) d->hinted = kHintFailed;  // decoded again from scratch (k_hintreset and the passes after it)
+      }
+    }
   }
   if (bad) atomicOr(&L.bad, 1);  // bad Huffman codes: libjpeg warns and decodes symbol 0 (statistics only)
   if (kStats) {
@@ -1634,9 +1680,11 @@ __device__ __forceinline__ void ent_phase(int img, int grp, ImgDesc* descs, cons
 // MODE 1: a small grid strides over the list and runs each image's groups in turn (LB = 10).  MODE 3:
 // (image, group) tasks of the LB = 11 images with ent_groups > 1, a grid of at most kTaskGrid
 // workgroups striding over them.  The sync pass is per image (MODE 0 for them too).
+// alt (MODE 0, or null): a list of the entry-point store's (sdsj_common.h kHintListHdr) taken instead of the
+// route's -- the images k_enthint left to the speculative and sync passes, or the retry list.
 template <int LB, int PHASE, int RT, int MODE, int NTS = kSyncThreads, int NSPEC = kEntThreads, bool CP = false>
 __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables, uint8_t* scratch, int32_t* routes,
-                                         int cap) {
+                                         int cap, const int32_t* alt = nullptr) {
   if (MODE == 3) {  // (image, group) tasks (k_plan's group_tasks list); a capped grid strides over them
     const int nt = routes[kRtEnt11G];
     const int32_t* tasks = group_tasks(routes, cap);
@@ -1647,8 +1695,8 @@ __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables
     }
     return;
   }
-  const int cnt = routes[RT];
-  const int32_t* list = route_list(routes, cap, RT);
+  const int cnt = MODE == 0 && alt ? (alt[0] < cap ? alt[0] : cap) : routes[RT];
+  const int32_t* list = MODE == 0 && alt ? alt + kHintListHdr : route_list(routes, cap, RT);
   if (MODE == 0) {  // one entry per workgroup at the full grid; a cold route's small grid strides (route_grid)
     for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
       ent_phase<LB, PHASE, NTS, NSPEC, CP>(list[li], 0, descs, tables, scratch);
@@ -1676,8 +1724,8 @@ __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables
 template <int LB, int RT, int MODE, int NSPEC = kEntThreads>
 __global__ void __launch_bounds__(NSPEC) __attribute__((amdgpu_waves_per_eu(LB == 11 ? SDSJ_SPEC_WAVES : 5)))
 k_entspec(ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables, uint8_t* __restrict__ scratch,
-          int32_t* __restrict__ routes, int cap) {
-  ent_feed<LB, 0, RT, MODE, kSyncThreads, NSPEC>(descs, tables, scratch, routes, cap);
+          int32_t* __restrict__ routes, int cap, const int32_t* __restrict__ alt) {
+  ent_feed<LB, 0, RT, MODE, kSyncThreads, NSPEC>(descs, tables, scratch, routes, cap, alt);
 }
 
 // Subsequences per lane of the speculative pass (one warm-up for the lane's run of them): the main
@@ -1694,15 +1742,19 @@ constexpr int kSpecThreadsG = kEntThreads / SDSJ_SPEC_SUBS_G;
 // (multi-group images have several times the sync tasks: a 4-wave workgroup runs them)
 template <int LB, int RT, int MODE, int NTS>
 __global__ void __launch_bounds__(NTS) k_entsync(ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
-                                                 uint8_t* __restrict__ scratch, int32_t* __restrict__ routes, int cap) {
-  ent_feed<LB, 1, RT, MODE, NTS>(descs, tables, scratch, routes, cap);
+                                                 uint8_t* __restrict__ scratch, int32_t* __restrict__ routes, int cap,
+                                                 const int32_t* __restrict__ alt) {
+  ent_feed<LB, 1, RT, MODE, NTS>(descs, tables, scratch, routes, cap, alt);
 }
 
+// (The waves per SIMD each variant's LDS allows.  For CP the target binds: the proof of stored entries keeps two
+// predictors alive past the decode loop, and left to itself the compiler then takes 102 VGPRs instead of 94 -- 4
+// waves.  Held to 96 it spills three registers, reloaded on the flagged-DC path and between images only.)
 template <int LB, int RT, int MODE, bool CP>
-__global__ void __launch_bounds__(kEntThreads) k_entwrite(ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
+__global__ void __launch_bounds__(kEntThreads) __attribute__((amdgpu_waves_per_eu(CP ? 5 : (LB == 11 ? 4 : 3)))) k_entwrite(ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
                                                           uint8_t* __restrict__ scratch, int32_t* __restrict__ routes,
-                                                          int cap) {
-  ent_feed<LB, 2, RT, MODE, kSyncThreads, kEntThreads, CP>(descs, tables, scratch, routes, cap);
+                                                          int cap, const int32_t* __restrict__ alt) {
+  ent_feed<LB, 2, RT, MODE, kSyncThreads, kEntThreads, CP>(descs, tables, scratch, routes, cap, alt);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1869,27 +1921,252 @@ __global__ void __launch_bounds__(kEntThreads) k_mh_select(ImgDesc* __restrict__
   if (t == 0) d->nsub = m.nsub;
 }
 
+// ------------------------------------------------------------------------------------------
+// Entry-point store (sdsj_common.h HintHdr): k_enthint before the speculative pass,
+// k_hintstore after the write pass and its retry.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long hint_key_at(const unsigned long long* keys, int64_t i) {
+  return __hip_atomic_load(&keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// An image the store serves: the single-group plan of the 11-bit route outside latency mode.
+__device__ __forceinline__ bool hint_eligible(const ImgDesc* d) { return !d->mh && !d->lat && d->ent_groups == 1; }
+
+// k_enthint, over the kRtEnt11 route (one workgroup per image): the subsequence layout, then the sample's record
+// by its address.  A record whose header equals the layout fills every subsequence's entry state as k_entsync
+// would leave it and marks the image hinted; every other image of the route goes to the lane's list for the
+// speculative and sync passes (lane[0] counts them).  What a record holds is trusted for nothing but memory
+// safety here (an entry inside its interval's bits, an MCU block of the image): k_entwrite proves the rest.
+__global__ void __launch_bounds__(kEntThreads) k_enthint(ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
+                                                         const int32_t* __restrict__ routes, int cap,
+                                                         const uint8_t* blob, const int64_t* __restrict__ offsets,
+                                                         const int32_t* __restrict__ lengths, HintStore hs,
+                                                         int32_t* __restrict__ lane) {
+  __shared__ int32_t tmp[kEntThreads];
+  __shared__ long long slot_s;
+  const int t = threadIdx.x;
+  const int cnt = routes[kRtEnt11];
+  const int32_t* list = route_list(routes, cap, kRtEnt11);
+  for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
+    const int img = list[li];
+    ImgDesc* d = &descs[img];
+    if (d->status != SDSJ_OK) continue;
+    bool hit = false;
+    if (hint_eligible(d)) {
+      const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
+      SubState* sub = reinterpret_cast<SubState*>(scratch + d->off_sub);
+      const int nsub = ent_layout<kEntThreads>(d, sv, sub, tmp);
+      const uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(blob + offsets[img]);
+      if (t == 0) {
+        long long slot = -1;
+        const int64_t slots = 2 * hs.rows;
+        int64_t i = (int64_t)(hint_hash(key) % (uint64_t)slots);
+        for (int p = 0; p < kHintProbes && p < slots; p++) {
+          const unsigned long long k = hint_key_at(hs.keys, i);
+          if (k == key) slot = (long long)__hip_atomic_load(&hs.ridx[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - 1;
+          if (k == key || k == 0) break;
+          i = i + 1 == slots ? 0 : i + 1;
+        }
+        slot_s = slot;
+      }
+      __syncthreads();  // (also: the layout's stores are visible to every thread)
+      const long long slot = slot_s;
+      const HintHdr* h = reinterpret_cast<const HintHdr*>(hs.recs + (slot < 0 ? 0 : slot) * kHintRowBytes);
+      bool ok = slot >= 0 && nsub <= kDecodeThreads;
+      ok = ok && h->key == key && h->length == lengths[img] && h->nsub == nsub && h->entropy_len == d->entropy_len &&
+           h->ulen == d->ulen && h->sub_bits == d->sub_bits && h->nseg == d->nseg && h->bpm == d->bpm;
+      uint4 r = make_uint4(0, 0, 0, 0);
+      if (ok && t < nsub) {
+        r = reinterpret_cast<const uint4*>(h + 1)[t];
+        const SubState& S = sub[t];
+        // an entry is the first block boundary at or after start_bit: past the interval's data it can only
+        // finish one block of zero bits (64 symbols of at most 27 bits)
+        if (!S.first)
+          ok = r.x >= S.start_bit && (uint64_t)r.x <= (uint64_t)S.lim_bit + 2048u && (r.y >> 24) < (uint32_t)d->bpm;
+      }
+      hit = __syncthreads_and(ok);  // (a record another lane is writing may read differently per thread)
+      if (hit && t < nsub) {
+        SubState& S = sub[t];
+        const bool f = S.first;  // exact by the layout: the interval's first bit, block 0, nothing before it
+        S.entry_p = f ? S.start_bit : r.x;
+        S.entry_bz = f ? (uint16_t)0 : (uint16_t)((r.y >> 24) << 8);
+        S.nblk_ex = f ? 0 : (int32_t)(r.y & 0xFFFFFFu);
+        S.dc_ex[0] = f ? 0 : (int32_t)(int16_t)(r.z & 0xFFFFu);
+        S.dc_ex[1] = f ? 0 : (int32_t)(int16_t)(r.z >> 16);
+        S.dc_ex[2] = f ? 0 : (int32_t)(int16_t)(r.w & 0xFFFFu);
+      }
+      if (hit && t == 0) {
+        d->nsub = nsub;
+        d->sync_rounds = h->sync_rounds;
+        d->pad0 = h->pad0;
+        d->hinted = kHintHit;
+      }
+    }
+    if (!hit && t == 0) {
+      const int k = atomicAdd(&lane[0], 1);
+      if (k < cap) lane[kHintListHdr + k] = img;
+    }
+    __syncthreads();  // LDS reuse by the next entry
+  }
+}
+
+// k_hintreset, over the kRtEnt11 route after the write pass (one thread per image): the images whose stored
+// entries failed its verification go to the lane's retry list, back in the state k_unstuff left them -- that
+// pass's last lanes may have set vend and kSegIns from wrong entries.  (Their coefficient blocks need nothing:
+// the retry stores every block up to vend again, a flagged one zeroes its hi slot first, and the dc / hi entries
+// of unflagged blocks are never read.)
+__global__ void __launch_bounds__(kEntThreads) k_hintreset(const ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
+                                                           const int32_t* __restrict__ routes, int cap,
+                                                           int32_t* __restrict__ retry) {
+  const int cnt = routes[kRtEnt11];
+  const int32_t* list = route_list(routes, cap, kRtEnt11);
+  for (int li = blockIdx.x * kEntThreads + threadIdx.x; li < cnt; li += gridDim.x * kEntThreads) {
+    const int img = list[li];
+    const ImgDesc* d = &descs[img];
+    if (d->status != SDSJ_OK || d->hinted != kHintFailed) continue;
+    const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
+    const int64_t bps = d->restart_interval ? (int64_t)d->restart_interval * d->bpm : d->total_blocks;
+    for (int k = 0; k < d->nseg; k++) {
+      const int64_t ge = (int64_t)(k + 1) * bps;
+      sv.vend[k] = (int32_t)(ge < d->total_blocks ? ge : d->total_blocks);
+      sv.flag[k] &= ~kSegIns;
+    }
+    const int k = atomicAdd(&retry[0], 1);
+    if (k < cap) retry[kHintListHdr + k] = img;
+  }
+}
+
+// k_hintstore, over the kRtEnt11 route after the write pass and its retry (a small grid strides over the list):
+// counts the images whose records were proved (hits), and records the verified entry states of every other
+// eligible image that decoded -- a miss, or a failed verification, whose row the fresh result overwrites.  An
+// image whose values do not fit the packed entries (sdsj_common.h HintHdr), or whose key finds no slot within
+// kHintProbes or no record left, is not recorded.  ctr: SDSJ_HINT_CTR_*.
+__global__ void __launch_bounds__(kEntThreads) k_hintstore(const ImgDesc* __restrict__ descs,
+                                                           const uint8_t* __restrict__ scratch,
+                                                           const int32_t* __restrict__ routes, int cap, const uint8_t* blob,
+                                                           const int64_t* __restrict__ offsets,
+                                                           const int32_t* __restrict__ lengths, HintStore hs,
+                                                           unsigned long long* __restrict__ ctr) {
+  __shared__ long long slot_s;
+  const int t = threadIdx.x;
+  const int cnt = routes[kRtEnt11];
+  const int32_t* list = route_list(routes, cap, kRtEnt11);
+  unsigned int n_hit = 0, n_miss = 0, n_fail = 0, n_stored = 0;  // (thread 0's)
+  for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
+    const int img = list[li];
+    const ImgDesc* d = &descs[img];
+    if (d->status != SDSJ_OK || !hint_eligible(d)) continue;
+    if (d->hinted == kHintHit) {
+      n_hit++;
+      continue;
+    }
+    if (d->hinted == kHintFailed) n_fail++;
+    else n_miss++;
+    const int nsub = d->nsub;
+    const SubState* sub = reinterpret_cast<const SubState*>(scratch + d->off_sub);
+    bool fits = nsub <= kDecodeThreads;
+    uint4 r = make_uint4(0, 0, 0, 0);
+    if (fits && t < nsub) {
+      const SubState& S = sub[t];
+      const int d0 = S.dc_ex[0], d1 = S.dc_ex[1], d2 = S.dc_ex[2];
+      fits = (S.entry_bz & 0xFF) == 0 && (uint32_t)S.nblk_ex < (1u << 24) && d0 == (int16_t)d0 && d1 == (int16_t)d1 &&
+             d2 == (int16_t)d2;
+      r = make_uint4(S.entry_p, ((uint32_t)(S.entry_bz >> 8) << 24) | ((uint32_t)S.nblk_ex & 0xFFFFFFu),
+                     ((uint32_t)d0 & 0xFFFFu) | ((uint32_t)d1 << 16), (uint32_t)d2 & 0xFFFFu);
+    }
+    fits = __syncthreads_and(fits);
+    const uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(blob + offsets[img]);
+    if (t == 0) {
+      long long slot = -1;
+      if (fits) {
+        const int64_t slots = 2 * hs.rows;
+        int64_t i = (int64_t)(hint_hash(key) % (uint64_t)slots);
+        for (int p = 0; p < kHintProbes && p < slots; p++) {
+          unsigned long long k = hint_key_at(hs.keys, i);
+          if (k == 0) {
+            k = atomicCAS(&hs.keys[i], 0ull, (unsigned long long)key);
+            if (k == 0) {  // this key's slot from now on: a record while there is room
+              const int r = atomicAdd(hs.count, 1);
+              if (r < hs.rows) __hip_atomic_store(&hs.ridx[i], r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              k = key;
+            }
+          }
+          if (k == key) {  // (no record: the store was full, or another lane is just taking the slot)
+            slot = (long long)__hip_atomic_load(&hs.ridx[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - 1;
+            break;
+          }
+          i = i + 1 == slots ? 0 : i + 1;
+        }
+      }
+      slot_s = slot;
+    }
+    __syncthreads();
+    const long long slot = slot_s;
+    if (slot >= 0) {
+      HintHdr* h = reinterpret_cast<HintHdr*>(hs.recs + slot * kHintRowBytes);
+      if (t < nsub) reinterpret_cast<uint4*>(h + 1)[t] = r;
+      if (t == 0) {
+        HintHdr v{};
+        v.key = key;
+        v.length = lengths[img];
+        v.nsub = nsub;
+        v.entropy_len = d->entropy_len;
+        v.ulen = d->ulen;
+        v.sub_bits = d->sub_bits;
+        v.nseg = d->nseg;
+        v.bpm = d->bpm;
+        v.sync_rounds = d->sync_rounds;
+        v.pad0 = d->pad0;
+        *h = v;
+        n_stored++;
+      }
+    }
+    __syncthreads();  // LDS reuse by the next entry
+  }
+  if (t == 0) {
+    if (n_hit) atomicAdd(&ctr[SDSJ_HINT_CTR_HITS], (unsigned long long)n_hit);
+    if (n_miss) atomicAdd(&ctr[SDSJ_HINT_CTR_MISSES], (unsigned long long)n_miss);
+    if (n_fail) atomicAdd(&ctr[SDSJ_HINT_CTR_VERIFY_FAILED], (unsigned long long)n_fail);
+    if (n_stored) atomicAdd(&ctr[SDSJ_HINT_CTR_STORED], (unsigned long long)n_stored);
+  }
+}
+
 size_t enttab_bytes() { return sizeof(EntTables); }
 
 constexpr int kTaskGrid = 4096;  // MODE 3 grid cap (>= the workgroups the chip holds at once)
 static int task_grid(int n) { return n * kMaxEntGroups < kTaskGrid ? n * kMaxEntGroups : kTaskGrid; }
+// With the entry-point store, the speculative and sync passes of the main route take the images k_enthint left
+// them: as few as none.  When the last batch's count that came back was zero (kRtHintMiss clear in the hint) they
+// get a small grid that strides over whatever the list holds; so do the retry passes, whose list is empty
+// unless samples changed in place.
+constexpr int kHintColdGrid = 1024;
+static unsigned hint_grid(const HintLane* hl, uint64_t hint, unsigned full) {
+  return hl && !route_on(hint, kRtHintMiss) && full > (unsigned)kHintColdGrid ? (unsigned)kHintColdGrid : full;
+}
 
 hipError_t launch_entspec(int n, ImgDesc* descs, const ImgTables* specs, void* etab, uint8_t* scratch, int32_t* routes,
-                          int cap, hipStream_t s, uint64_t rm, bool small, uint64_t hint) {
+                          int cap, hipStream_t s, uint64_t rm, bool small, uint64_t hint, const HintLane* hl) {
   const int g = n;  // one workgroup per image on the main route
   EntTables* tables = static_cast<EntTables*>(etab);
   const int gs = g < 256 ? g : 256;
   if (route_on(rm, kRtEnt11) || route_on(rm, kRtEnt11M) || route_on(rm, kRtEnt10))
     hipLaunchKernelGGL(k_enttab, dim3(n), dim3(kEntThreads), 0, s, descs, specs, tables);
-  if (route_on(rm, kRtEnt11))
-    hipLaunchKernelGGL((k_entspec<11, kRtEnt11, 0, kSpecThreads>), dim3(route_grid(hint, kRtEnt11, g)), dim3(kSpecThreads), 0,
-                       s, descs, tables, scratch, routes, cap);
+  if (route_on(rm, kRtEnt11)) {
+    if (hl) {  // the store's lookup first: the speculative pass takes what it leaves (the lane's list)
+      if (hipMemsetAsync(hl->lane, 0, sizeof(int32_t) * kHintListHdr, s) != hipSuccess ||
+          hipMemsetAsync(hint_retry_list(hl->lane, cap), 0, sizeof(int32_t) * kHintListHdr, s) != hipSuccess)
+        return hipGetLastError();
+      hipLaunchKernelGGL(k_enthint, dim3(route_grid(hint, kRtEnt11, g)), dim3(kEntThreads), 0, s, descs, scratch, routes, cap,
+                         hl->blob, hl->offsets, hl->lengths, hl->store, hl->lane);
+    }
+    hipLaunchKernelGGL((k_entspec<11, kRtEnt11, 0, kSpecThreads>), dim3(hint_grid(hl, hint, route_grid(hint, kRtEnt11, g))),
+                       dim3(kSpecThreads), 0, s, descs, tables, scratch, routes, cap, hl ? hl->lane : nullptr);
+  }
   if (route_on(rm, kRtEnt11M))
     hipLaunchKernelGGL((k_entspec<11, kRtEnt11M, 3, kSpecThreadsG>), dim3(route_grid(hint, kRtEnt11M, task_grid(n))),
-                       dim3(kSpecThreadsG), 0, s, descs, tables, scratch, routes, cap);
+                       dim3(kSpecThreadsG), 0, s, descs, tables, scratch, routes, cap, nullptr);
   if (route_on(rm, kRtEnt10))
     hipLaunchKernelGGL((k_entspec<10, kRtEnt10, 1>), dim3(route_grid(hint, kRtEnt10, gs)), dim3(kEntThreads), 0, s, descs,
-                       tables, scratch, routes, cap);
+                       tables, scratch, routes, cap, nullptr);
   if (SDSJ_MH && small) {  // latency-mode images (ImgDesc::mh; the kernels above skip them)
     constexpr int kMhGridY = 64;
     if (route_on(rm, kRtEnt11)) {
@@ -1905,41 +2182,57 @@ hipError_t launch_entspec(int n, ImgDesc* descs, const ImgTables* specs, void* e
 }
 
 hipError_t launch_entsync(int n, ImgDesc* descs, void* etab, uint8_t* scratch, int32_t* routes, int cap, hipStream_t s,
-                          uint64_t rm, uint64_t hint) {
+                          uint64_t rm, uint64_t hint, const HintLane* hl) {
   const int g = n;
   EntTables* tables = static_cast<EntTables*>(etab);
   const int gs = g < 256 ? g : 256;
   if (route_on(rm, kRtEnt11))
-    hipLaunchKernelGGL((k_entsync<11, kRtEnt11, 0, kSyncThreads>), dim3(route_grid(hint, kRtEnt11, g)), dim3(kSyncThreads), 0,
-                       s, descs, tables, scratch, routes, cap);
+    hipLaunchKernelGGL((k_entsync<11, kRtEnt11, 0, kSyncThreads>), dim3(hint_grid(hl, hint, route_grid(hint, kRtEnt11, g))),
+                       dim3(kSyncThreads), 0, s, descs, tables, scratch, routes, cap, hl ? hl->lane : nullptr);
   if (route_on(rm, kRtEnt11M))
     hipLaunchKernelGGL((k_entsync<11, kRtEnt11M, 0, kEntThreads>), dim3(route_grid(hint, kRtEnt11M, g)), dim3(kEntThreads), 0,
-                       s, descs, tables, scratch, routes, cap);
+                       s, descs, tables, scratch, routes, cap, nullptr);
   if (route_on(rm, kRtEnt10))
     hipLaunchKernelGGL((k_entsync<10, kRtEnt10, 1, kSyncThreads>), dim3(route_grid(hint, kRtEnt10, gs)), dim3(kSyncThreads), 0,
-                       s, descs, tables, scratch, routes, cap);
+                       s, descs, tables, scratch, routes, cap, nullptr);
   return hipGetLastError();
 }
 
 hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scratch, int32_t* routes, int cap,
-                           hipStream_t s, uint64_t rm, uint64_t hint, bool small) {
+                           hipStream_t s, uint64_t rm, uint64_t hint, bool small, const HintLane* hl) {
   const int g = n;  // one workgroup per image on the main route
   const EntTables* tables = static_cast<const EntTables*>(etab);
+  const int32_t* no_alt = nullptr;
   const int gs = g < 256 ? g : 256;
   // (latency-mode lanes keep the int16 coefficient format: coef_compact)
   if (route_on(rm, kRtEnt11)) {
     const dim3 grid(route_grid(hint, kRtEnt11, g));
-    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
-    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
+    int32_t* retry = hl ? hint_retry_list(hl->lane, cap) : nullptr;
+    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
+    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
+    if (hl) {
+      // the images whose stored entries the write pass refuted (none unless samples changed in place): the
+      // ordinary passes over the retry list, from the state the refuted pass found (k_hintreset), then the
+      // records of everything that decoded without a proved hit
+      const dim3 rg(g < kHintColdGrid ? g : kHintColdGrid);
+      hipLaunchKernelGGL(k_hintreset, dim3((g + kEntThreads - 1) / kEntThreads), dim3(kEntThreads), 0, s, descs, scratch, routes,
+                         cap, retry);
+      hipLaunchKernelGGL((k_entspec<11, kRtEnt11, 0, kSpecThreads>), rg, dim3(kSpecThreads), 0, s, descs, tables, scratch, routes, cap, retry);
+      hipLaunchKernelGGL((k_entsync<11, kRtEnt11, 0, kSyncThreads>), rg, dim3(kSyncThreads), 0, s, descs, tables, scratch, routes, cap, retry);
+      if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), rg, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, retry);
+      else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), rg, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, retry);
+      hipLaunchKernelGGL(k_hintstore, dim3(g < 256 ? g : 256), dim3(kEntThreads), 0, s, descs, scratch, routes, cap, hl->blob,
+                         hl->offsets, hl->lengths, hl->store, hl->ctr);
+    }
   }
   if (route_on(rm, kRtEnt11M)) {
     const dim3 grid(route_grid(hint, kRtEnt11M, task_grid(n)));
-    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
-    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap);
+    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
+    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
   }
   if (route_on(rm, kRtEnt10))
     hipLaunchKernelGGL((k_entwrite<10, kRtEnt10, 1, false>), dim3(route_grid(hint, kRtEnt10, gs)), dim3(kEntThreads), 0, s, descs,
-                       tables, scratch, routes, cap);
+                       tables, scratch, routes, cap, no_alt);
   return hipGetLastError();
 }
 

@@ -67,18 +67,30 @@ void launch_coef_zero(int rt, int n, const ImgDesc* descs, uint8_t* scratch, con
 hipError_t launch_scans(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
                         const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                         uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
+// The entry-point store for one lane of the device-resident path (sdsj_common.h HintHdr; null: off): the
+// store, the lane's work lists (hint_lane_ints) and the engine's SDSJ_HINT_CTR_* counters, and the lane's
+// samples, whose addresses are the keys.
+struct HintLane {
+  HintStore store;
+  int32_t* lane;
+  unsigned long long* ctr;
+  const uint8_t* blob;
+  const int64_t* offsets;
+  const int32_t* lengths;
+};
 size_t enttab_bytes();  // per-image decode tables (k_enttab) held in HBM between the entropy kernels
 // k_enttab (decode tables) + k_entspec (subsequence layout, warm-up, speculative decode)
 // (small: a host-path latency-mode chunk, where ImgDesc::mh images take the multi-hypothesis pass)
 hipError_t launch_entspec(int n, ImgDesc* descs, const ImgTables* specs, void* etab, uint8_t* scratch, int32_t* routes,
                           int cap, hipStream_t s, uint64_t rm = kAllRoutes, bool small = false,
-                          uint64_t hint = kAllRoutes);
+                          uint64_t hint = kAllRoutes, const HintLane* hl = nullptr);
 // k_entsync (sync rounds + segmented scan)
 hipError_t launch_entsync(int n, ImgDesc* descs, void* etab, uint8_t* scratch, int32_t* routes, int cap, hipStream_t s,
-                          uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
+                          uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes, const HintLane* hl = nullptr);
 // (small: as for launch_entspec -- the lane's images are in latency mode and keep int16 coefficient blocks)
 hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scratch, int32_t* routes, int cap,
-                           hipStream_t s, uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes, bool small = false);
+                           hipStream_t s, uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes, bool small = false,
+                           const HintLane* hl = nullptr);
 hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s);
 hipError_t launch_color(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                         uint64_t rm = kAllRoutes);

@@ -147,6 +147,7 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   const int slots = frames || png ? 2 * kMaxComp : huff_slots(*d);
   d->mh = (int8_t)(SDSJ_MH && d->lat && !d->progressive && d->restart_interval == 0 && d->bpm <= kMhMaxPhases &&
                    slots <= 4);
+  d->hinted = 0;  // (k_enthint sets it)
   {
     const int64_t bits = d->entropy_len * 8;
     const int64_t per_group = (int64_t)kDecodeThreads * (d->lat ? kLatSubBits : kGroupBits);

@@ -132,7 +132,9 @@ def _device_index(device) -> int:
 class JpegEngine:
     """Owns one native ``sdsj_engine`` bound to one HIP device."""
 
-    def __init__(self, device=None, max_batch: int = 4096, scratch_bytes: int = 0):
+    def __init__(self, device=None, max_batch: int = 4096, scratch_bytes: int = 0, *, hint_rows: Optional[int] = None):
+        """``hint_rows``: rows of the entry-point store the device-resident path keeps (include/sdsj.h
+        sdsj_engine_set_hints); None: the native default, 2 x max_batch; 0: no store."""
         if not torch.cuda.is_available():
             raise RuntimeError("sds_amd needs a ROCm GPU (torch.cuda.is_available() is False)")
         self.lib = _lib.load()
@@ -149,6 +151,8 @@ class JpegEngine:
         self._inflight: dict[int, tuple[torch.Tensor, int]] = {}
         self._fallback = 0  # samples the transforms decoded with PIL on the host (counters()["fallback"])
         self._formats = _lib.FORMAT_JPEG  # the native engine's current mask (sdsj_engine_set_formats)
+        if hint_rows is not None:
+            self._check(self.lib.sdsj_engine_set_hints(self._h, int(hint_rows)), "sdsj_engine_set_hints")
 
     # -- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -396,10 +400,18 @@ class JpegEngine:
         self._check(self.lib.sdsj_engine_counters(self._h, buf, _lib.NUM_COUNTERS, int(bool(reset))),
                     "sdsj_engine_counters")
         out = {self.lib.sdsj_counter_name(k).decode(): int(buf[k]) for k in range(_lib.NUM_COUNTERS)}
+        hbuf = (ctypes.c_uint64 * _lib.NUM_HINT_COUNTERS)()  # the entry-point store's (hint_hits, ...)
+        self._check(self.lib.sdsj_engine_hint_counters(self._h, hbuf, _lib.NUM_HINT_COUNTERS, int(bool(reset))),
+                    "sdsj_engine_hint_counters")
+        out.update({self.lib.sdsj_hint_counter_name(k).decode(): int(hbuf[k]) for k in range(_lib.NUM_HINT_COUNTERS)})
         out["fallback"] = self._fallback
         if reset:
             self._fallback = 0
         return out
+
+    def clear_hints(self) -> None:
+        """Empties the entry-point store: every row decodes the full way once more.  Waits for the device."""
+        self._check(self.lib.sdsj_engine_clear_hints(self._h), "sdsj_engine_clear_hints")
 
     def note_fallback(self, n: int = 1) -> None:
         """Counts samples decoded by PIL on the host and resized by this engine (the transforms' rerun of
