@@ -143,13 +143,28 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * coefficients), a scan without restart intervals that holds fill bytes before a stuffed zero SDSJ_CORRUPT.
  * A file that ends at EOI before every component was coded decodes, the missing components from zero
  * coefficients, as in PIL.  Samplings with ratios of 3 and 4 and RGB-coded files need SDSJ_FORMAT_JPEG_EXT as
- * well.  Without the bit nothing changes: multi-scan sequential files report SDSJ_UNSUPPORTED. */
+ * well.  Without the bit nothing changes: multi-scan sequential files report SDSJ_UNSUPPORTED.
+ *
+ * SDSJ_FORMAT_GIF is a third base format (valid alone or with any other bit): GIF87a / GIF89a, the first
+ * frame on the logical screen, giving the pixels of PIL.Image.open(...).convert("RGB") -- the local colour
+ * table if there is one, else the global one, indices at or beyond its entries black, where a table that is
+ * the identity grey ramp counts as none; without a table (index, index, index); pixels outside the frame rectangle in the colour of index
+ * 0, or of the transparent index when a graphic-control extension before the image sets one; interlaced
+ * frames; LZW minimum code sizes 2..8.  The blocks before the first image descriptor must be well formed
+ * (graphic-control, comment, application and plain-text extensions are walked by their sub-blocks), the
+ * frame non-empty and inside the screen; nothing after the frame's data is read.  A frame that leaves the
+ * screen, another code size, a file without an image descriptor and an unknown block report
+ * SDSJ_UNSUPPORTED; an empty screen or frame, a sub-block past the input, an end code or the end of the
+ * data before the last pixel, a code above the next free entry and a first code after a clear that is no
+ * literal report SDSJ_CORRUPT (PIL raises on the truncated ones).  Callers rerun both on PIL.  Without the
+ * bit nothing changes: a GIF reports SDSJ_UNSUPPORTED. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
 #define SDSJ_FORMAT_PNG_EXT 4
 #define SDSJ_FORMAT_PNG_META 16
 #define SDSJ_FORMAT_JPEG_EXT 64
 #define SDSJ_FORMAT_JPEG_SCANS 128
+#define SDSJ_FORMAT_GIF 256 /* (bits 8 and 32 are not formats: SDSJ_EINVAL) */
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -167,8 +182,23 @@ int sdsj_png_probe(const uint8_t* png, size_t n, sdsj_png_info* out);
  * compressed chunks and the chunks after the image data are judged too (the whole file is walked). */
 int sdsj_png_probe_formats(const uint8_t* png, size_t n, int formats, sdsj_png_info* out);
 
+typedef struct sdsj_gif_info {
+    int32_t width, height;                      /* the logical screen: the image's size */
+    int32_t frame_x, frame_y, frame_w, frame_h; /* the first image descriptor's rectangle */
+    int32_t interlace;
+    int32_t table_entries; /* entries of the effective colour table; 0: grey (no table, or the identity ramp) */
+    int32_t min_code_size; /* LZW minimum code size */
+    int32_t supported;     /* 1 if the MI355X path decodes it (when GIF is enabled) */
+} sdsj_gif_info;
+
+/* Host-side parse of one GIF up to its first data sub-block (no GPU needed): the screen's size as soon as
+ * it is readable, the other fields once the first image descriptor has been read, and the status k_parse
+ * gives the sample with SDSJ_FORMAT_GIF enabled (the LZW data is the device's to judge). */
+int sdsj_gif_probe(const uint8_t* gif, size_t n, sdsj_gif_info* out);
+
 /* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
- * has SDSJ_FORMAT_PNG (a format outside the mask reports SDSJ_UNSUPPORTED, need 0).  With
+ * has SDSJ_FORMAT_PNG and GIF samples when it has SDSJ_FORMAT_GIF (a format outside the mask reports
+ * SDSJ_UNSUPPORTED, need 0).  With
  * SDSJ_FORMAT_JPEG_SCANS a multi-scan sequential file that is refused over its scans (not its header: a scan that
  * is not a sequential one, a component coded twice, fill bytes before a stuffed zero) reports that status together
  * with the bytes the device plans for it before it refuses it: a batch that holds the file needs them. */
@@ -179,7 +209,7 @@ int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int 
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out);
 int sdsj_engine_destroy(sdsj_engine* eng);
 
-/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG and PNG) the engine decodes in batches submitted after the
+/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG, PNG and GIF) the engine decodes in batches submitted after the
  * call, on every decode entry point: sdsj_decode_resize_batch, sdsj_decode_resize_batch_device,
  * sdsj_submit_batch, sdsj_submit_files (and so what sdsj_wait_batch reports).  Default: JPEG only. */
 int sdsj_engine_set_formats(sdsj_engine* eng, int mask);

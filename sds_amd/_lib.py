@@ -35,12 +35,13 @@ EXPORTS = [
     "sdsj_submit_files", "sdsj_wait_batch", "sdsj_engine_counters", "sdsj_counter_name", "sdsj_engine_set_lanes",
     "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve", "sdsj_engine_set_formats", "sdsj_png_probe",
     "sdsj_plan_need_formats", "sdsj_png_probe_formats", "sdsj_probe_formats", "sdsj_engine_set_hints",
-    "sdsj_engine_clear_hints", "sdsj_engine_hint_counters", "sdsj_hint_counter_name",
+    "sdsj_engine_clear_hints", "sdsj_engine_hint_counters", "sdsj_hint_counter_name", "sdsj_gif_probe",
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
 NUM_HINT_COUNTERS = 4  # SDSJ_NUM_HINT_COUNTERS (the entry-point store's: sdsj_engine_hint_counters)
 FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META, FORMAT_JPEG_EXT = 1, 2, 4, 16, 64  # SDSJ_FORMAT_*
 FORMAT_JPEG_SCANS = 128
+FORMAT_GIF = 256
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
 # valid only together with PNG, so the name carries both
 # "png-meta": PNG files as converters and editors write them (iCCP, zTXt, iTXt, chunks after the image data);
@@ -49,15 +50,18 @@ FORMAT_JPEG_SCANS = 128
 # RGB-coded files); the bit is valid only together with JPEG, so the name carries both
 # "jpeg-scans": multi-scan sequential JPEG (SOF0 / SOF1 frames whose components arrive in more than one scan, as
 # jpegtran -scans writes them); likewise valid only together with JPEG, and combinable with "jpeg-ext"
+# "gif": the first frame of a GIF87a / GIF89a file; a base format of its own, valid alone and with every other name
 FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT,
            "png-meta": FORMAT_PNG | FORMAT_PNG_META, "jpeg-ext": FORMAT_JPEG | FORMAT_JPEG_EXT,
-           "jpeg-scans": FORMAT_JPEG | FORMAT_JPEG_SCANS}
+           "jpeg-scans": FORMAT_JPEG | FORMAT_JPEG_SCANS, "gif": FORMAT_GIF}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+GIF_SIGNATURES = (b"GIF87a", b"GIF89a")
 
 
 def format_mask(formats) -> int:
-    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "png" / "png-ext" / "png-meta" (None: JPEG
-    only, the engine's default).  "jpeg-ext" and "jpeg-scans" include "jpeg", as "png-ext" and "png-meta" include "png"."""
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "png" / "png-ext" / "png-meta" / "gif"
+    (None: JPEG only, the engine's default).  "jpeg-ext" and "jpeg-scans" include "jpeg", as "png-ext" and "png-meta"
+    include "png"; "gif" stands alone or beside any of them."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):
@@ -87,6 +91,13 @@ class SdsjInfo(ctypes.Structure):
 class SdsjPngInfo(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32),
                 ("color_type", ctypes.c_int32), ("interlace", ctypes.c_int32), ("supported", ctypes.c_int32)]
+
+
+class SdsjGifInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("frame_x", ctypes.c_int32),
+                ("frame_y", ctypes.c_int32), ("frame_w", ctypes.c_int32), ("frame_h", ctypes.c_int32),
+                ("interlace", ctypes.c_int32), ("table_entries", ctypes.c_int32), ("min_code_size", ctypes.c_int32),
+                ("supported", ctypes.c_int32)]
 
 
 class SdsjCfg(ctypes.Structure):
@@ -165,6 +176,7 @@ def load() -> ctypes.CDLL:
         lib.sdsj_engine_set_formats.argtypes = [vp, ctypes.c_int]
         lib.sdsj_png_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjPngInfo)]
         lib.sdsj_png_probe_formats.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, ctypes.POINTER(SdsjPngInfo)]
+        lib.sdsj_gif_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjGifInfo)]
         lib.sdsj_plan_need_formats.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjOp), ctypes.c_int,
                                                ctypes.POINTER(i64)]
         for name in EXPORTS:
@@ -195,4 +207,12 @@ def png_probe(png: bytes, formats=None) -> tuple[int, SdsjPngInfo]:
         st = load().sdsj_png_probe(png, len(png), ctypes.byref(info))
     else:
         st = load().sdsj_png_probe_formats(png, len(png), int(formats), ctypes.byref(info))
+    return st, info
+
+
+def gif_probe(gif: bytes) -> tuple[int, SdsjGifInfo]:
+    """sdsj_gif_probe: the screen, the first frame's rectangle and the status the sample gets under "gif" before its
+    LZW data is decoded."""
+    info = SdsjGifInfo()
+    st = load().sdsj_gif_probe(gif, len(gif), ctypes.byref(info))
     return st, info

@@ -237,6 +237,7 @@ struct ImgDesc {
   // png_bpp); with SDSJ_FORMAT_PNG_EXT the sum of png_layout's passes, png_bpp being the filter unit)
   // from the IDAT chain at png_idat_pos, k_png_unfilter / k_png_unfilter_ext write the RGB rows at
   // off_rgb.  Bit depth and interlace travel in png_depth_lace (the struct's size and offsets are pinned).
+  // png == 2 (kGifSample): a GIF sample (sdsj_gif.h gif_fill_desc says what each field carries then).
   int32_t png;
   int32_t png_ctype, png_bpp, png_plte_n;  // colour type, filter unit (bytes per pixel, 1 below depth 8), PLTE entries
   int64_t png_plte_pos, png_idat_pos;      // relative to the sample's first byte
@@ -381,6 +382,7 @@ enum Route : int32_t {
   kRtUsSmall, kRtUsBig,           // unstuffing: k_us_serial / the tile-parallel passes (kUsSerialTiles)
   kRtPng,                         // PNG samples (k_png_inflate, k_png_unfilter); they resample through kRtUnfused
   kRtScans,                       // multi-scan sequential images (k_scans; ImgDesc::progressive == kScansSequential)
+  kRtGif,                         // GIF samples (k_gif_lzw, k_gif_rgb; SDSJ_FORMAT_GIF); they resample through kRtUnfused
   kNumRoutes
 };
 constexpr int kRouteSlots = 48;  // counts [0, kNumRoutes), the rest zero

@@ -245,6 +245,8 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   if (e->formats & SDSJ_FORMAT_JPEG_SCANS)  // (counts under the progressive stage)
     SDSJ_HIP(e, launch_scans(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (evs) (void)hipEventRecord((*evs)[kPngEvent].get(), s);
+  if (e->formats & SDSJ_FORMAT_GIF)  // (counts under "png_inflate")
+    SDSJ_HIP(e, launch_gif(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (e->formats & SDSJ_FORMAT_PNG)
     SDSJ_HIP(e, launch_png(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint,
                            evs ? (*evs)[kPngEvent + 1].get() : nullptr, e->formats));
@@ -734,12 +736,12 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
   return st;
 }
 
-// A format mask names at least one of JPEG and PNG, nothing unknown, PNG_EXT and PNG_META (alone or
+// A format mask names at least one of JPEG, PNG and GIF, nothing unknown, PNG_EXT and PNG_META (alone or
 // together) only with PNG, and JPEG_EXT and JPEG_SCANS (alone or together) only with JPEG.
 static bool valid_formats(int mask) {
   const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS;
-  const int all = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | sub | jsub;
-  return (mask & (SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG)) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
+  const int base = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_GIF, all = base | sub | jsub;
+  return (mask & base) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
          (!(mask & jsub) || (mask & SDSJ_FORMAT_JPEG));
 }
 

@@ -32,6 +32,10 @@ hipError_t launch_parse(int n, const uint8_t* blob, int64_t blob_bytes, const in
 hipError_t launch_png(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                       uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
                       uint64_t hint = kAllRoutes, hipEvent_t between = nullptr, int formats = SDSJ_FORMAT_PNG);
+// GIF samples (route kRtGif; engines with SDSJ_FORMAT_GIF): k_gif_lzw then k_gif_rgb (sdsj_gif.hip)
+hipError_t launch_gif(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                      uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
+                      uint64_t hint = kAllRoutes);
 // launch_png's kernels of the wider subset (sdsj_png_ext.hip); g: launch_png's grid
 void launch_png_inflate_ext(unsigned g, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                             uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "sdsj_common.h"
+#include "sdsj_gif.h"
 #include "sdsj_png.h"
 
 namespace sdsj {
@@ -202,9 +203,9 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
 // progressive images), entropy variant by the Huffman tables in use (slots as load_tables counts
 // them), resample variant as plan_image chose it (-1 for an empty crop).
 SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
-  if (d.png) {
+  if (d.png) {  // (a PNG, or a GIF: kGifSample)
     *ru = -1;
-    *re = kRtPng;
+    *re = d.png == kGifSample ? kRtGif : kRtPng;
     *rr = d.geo == kGeoZeros ? -1 : kRtUnfused;
     return;
   }
@@ -292,7 +293,7 @@ SDSJ_HD inline bool scan_tables_ok(const ImgDesc& d, const ImgTables& t) {
   return true;
 }
 
-// One sample, from its bytes to its plan: a PNG (where the engine's formats enable it) is parsed and
+// One sample, from its bytes to its plan: a PNG or a GIF (where the engine's formats enable it) is parsed and
 // planned for the unfused passes, everything else is a JPEG or SDSJ_UNSUPPORTED.  Returns the status;
 // *d is planned (d->need, the off_* fields, what image_routes reads) only when it is SDSJ_OK.  Table
 // validation is not part of it: the device's sink defers the table bytes (k_parse validates once all
@@ -306,6 +307,13 @@ SDSJ_HD int plan_sample(const Reader& rd, int64_t n, const sdsj_op& op, bool sma
     PngHdr ph;
     status = png_parse(rd, n, &ph, formats);
     png_fill_desc(d, ph);
+    if (status == SDSJ_OK) plan_image(d, op, false, false, true);
+  } else if ((formats & SDSJ_FORMAT_GIF) && gif_signature(rd, n)) {
+    // (planned like a PNG: the index buffer takes off_png -- png_raw = width x height bytes --, k_gif_rgb
+    // packs the RGB rows at off_rgb)
+    GifHdr gh;
+    status = gif_parse(rd, n, &gh);
+    gif_fill_desc(d, gh);
     if (status == SDSJ_OK) plan_image(d, op, false, false, true);
   } else if (!(formats & SDSJ_FORMAT_JPEG)) {
     status = SDSJ_UNSUPPORTED;

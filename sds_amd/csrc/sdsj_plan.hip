@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(256) k_finish(int n, const ImgDesc* __restrict
       if (lengths && lengths[img] > 0) atomicAdd(&acc[SDSJ_CTR_BYTES_IN], (unsigned long long)lengths[img]);
       atomicAdd(&acc[SDSJ_CTR_BYTES_OUT], (unsigned long long)(total * (op.out_dtype == SDSJ_DTYPE_F32 ? 4 : 1)));
       if (lengths && st == SDSJ_OK && d->progressive == 1) atomicAdd(&acc[SDSJ_CTR_PROGRESSIVE], 1ull);
-      if (lengths && st == SDSJ_OK && d->png) atomicAdd(&acc[SDSJ_CTR_PNG], 1ull);
+      if (lengths && st == SDSJ_OK && d->png == 1) atomicAdd(&acc[SDSJ_CTR_PNG], 1ull);  // (2: a GIF sample)
     }
   }
   __syncthreads();
@@ -344,7 +344,7 @@ int64_t host_plan_need(const uint8_t* jpg, int64_t n, const sdsj_op& op, int* st
   MemReader rd{jpg};
   int st = plan_sample(rd, n, op, small, formats, &d, &t, CopySink<MemReader>{rd});
   // (the device runs this check in a kernel of its own between k_parse and k_plan: launch_png_meta)
-  if (st == SDSJ_OK && d.png && (formats & SDSJ_FORMAT_PNG_META)) st = host_png_meta(jpg, n, d.png_idat_pos, formats);
+  if (st == SDSJ_OK && d.png == 1 && (formats & SDSJ_FORMAT_PNG_META)) st = host_png_meta(jpg, n, d.png_idat_pos, formats);
   *status = st;
   if (later) *later = st == SDSJ_OK && !d.png && d.progressive == kScansSequential ? scans_check(rd, n, d) : SDSJ_OK;
   if (routes) {

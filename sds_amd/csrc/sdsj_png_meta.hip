@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
   const int img = blockIdx.x, lane = threadIdx.x;
   if (img >= n) return;
   ImgDesc* d = &descs[img];
-  if (d->status != SDSJ_OK || !d->png) return;
+  if (d->status != SDSJ_OK || d->png != 1) return;  // (2: a GIF sample)
   const WindowReader rd{blob + offsets[img], (int64_t)lengths[img], win, lane, -(int64_t)4 * kWin};
   const int st = png_meta_check(rd, rd.n, d->png_idat_pos, formats, &T);
   if (st != SDSJ_OK && lane == 0) d->status = st;
