@@ -226,8 +226,8 @@ struct ImgDesc {
   union {
     int8_t sm_pad[3];
     // entry-point store (HintHdr below), in the first pad byte (the struct's size and offsets are pinned):
-    // kHintHit = k_enthint filled the SubStates from a record, kHintFailed = k_entwrite's verification
-    // refused them (the image goes to the retry list)
+    // kHintHit = k_enthint found the image's record (k_entwrite takes its entries from it; no SubState is laid
+    // out), kHintFailed = k_entwrite's verification refused them (the image goes to the retry list)
     int8_t hinted;
   };
   int32_t etab;  // k_enttab: the image whose EntTables it decodes with (itself, or image 0 of the lane when equal)
@@ -332,10 +332,64 @@ SDSJ_HD inline uint64_t hint_hash(uint64_t key) {
 // Per-lane work lists of the store (int32): two blocks of kHintListHdr + cap entries, [0] = the count --
 // the route's images k_enthint left to the speculative and sync passes, then the images whose records
 // failed k_entwrite's verification.
+// Then cap entries listing the eligible images that decoded without a proved hit (k_hintreset; their count
+// in the retry list's header, [kHintStoreCnt]: k_hintstore records them), and cap entries indexed by image:
+// the record k_enthint found for a hit image, where k_entwrite reads its entries.
 constexpr int kHintListHdr = 16;
-SDSJ_HD inline int64_t hint_lane_ints(int cap) { return 2 * ((int64_t)kHintListHdr + cap); }
+constexpr int kHintStoreCnt = 1;
+SDSJ_HD inline int64_t hint_lane_ints(int cap) { return 2 * ((int64_t)kHintListHdr + cap) + 2 * (int64_t)cap; }
 SDSJ_HD inline int32_t* hint_retry_list(int32_t* lane, int cap) { return lane + kHintListHdr + cap; }
+SDSJ_HD inline int32_t* hint_store_list(int32_t* lane, int cap) { return lane + 2 * ((int64_t)kHintListHdr + cap); }
+SDSJ_HD inline int32_t* hint_rec_index(int32_t* lane, int cap) { return hint_store_list(lane, cap) + cap; }
 constexpr int kRtHintMiss = 62;      // bit of a route hint (no route): the speculative pass had images last time
+
+// The subsequence layout by subsequence (what ent_layout of sdsj_entropy.hip stores for every one of them):
+// restart interval s holds sub_count() subsequences, off[s] of them come before it (an exclusive sum), and
+// subsequence j belongs to the last interval with off[s] <= j.
+struct SubLayout {
+  uint32_t start_bit, end_bit, lim_bit;
+  int32_t seg;
+  bool first, last;  // of its interval (last: also the image's last one, where nsub_cap cut the interval short)
+};
+SDSJ_HD inline int sub_count(int32_t lo, int32_t hi, uint32_t sub_bits) {
+  const uint32_t b0 = (uint32_t)lo * 8u;
+  uint32_t b1 = (uint32_t)hi * 8u;
+  if (b1 < b0) b1 = b0;
+  return b1 > b0 ? (int)((b1 - b0 + sub_bits - 1) / sub_bits) : 1;
+}
+SDSJ_HD inline int sub_total(int64_t sum, int nsub_cap) { return sum < nsub_cap ? (int)sum : nsub_cap; }
+// (off: strictly increasing, off[0] = 0 -- every interval has a subsequence)
+SDSJ_HD inline int sub_interval(const int32_t* off, int nseg, int j) {
+  int a = 0, b = nseg;  // the answer is in [a, b)
+  while (b - a > 1) {
+    const int mid = (a + b) >> 1;
+    if (off[mid] <= j) a = mid;
+    else b = mid;
+  }
+  return a;
+}
+// Subsequence j of nsub, the k-th of interval s (bytes [lo, hi))
+SDSJ_HD inline SubLayout sub_layout(int32_t lo, int32_t hi, uint32_t sub_bits, int s, int k, int j, int nsub) {
+  SubLayout o;
+  const uint32_t b0 = (uint32_t)lo * 8u;
+  uint32_t b1 = (uint32_t)hi * 8u;
+  if (b1 < b0) b1 = b0;
+  o.start_bit = b0 + (uint32_t)k * sub_bits;
+  const uint32_t e = o.start_bit + sub_bits;
+  o.end_bit = e < b1 ? e : b1;
+  o.lim_bit = b1;
+  o.seg = s;
+  o.first = k == 0;
+  o.last = j + 1 == nsub || k + 1 == sub_count(lo, hi, sub_bits);
+  return o;
+}
+// What a stored entry (HintHdr's packed form) is trusted for before k_entwrite starts from it -- memory safety,
+// nothing else: a bit inside its interval's data or the one block of zero bits past it that a lane can finish
+// there (64 symbols of at most 27 bits), and an MCU block of the image.  An interval's first subsequence takes
+// no entry from the record: it is exact by the layout.
+SDSJ_HD inline bool hint_entry_safe(uint32_t x, uint32_t y, const SubLayout& o, int bpm) {
+  return o.first || (x >= o.start_bit && (uint64_t)x <= (uint64_t)o.lim_bit + 2048u && (y >> 24) < (uint32_t)bpm);
+}
 
 // Restart-interval table (scratch at off_seg).  Interval k = the k-th restart interval (the whole
 // scan without DRI).  k_unstuff fills [lo[k], hi[k]) = the unstuffed bytes it decodes, chosen the way

@@ -1308,8 +1308,15 @@ __device__ __attribute__((noinline)) void store_flagged_dc(uint8_t* hslot, int16
 // the compact format (the 64-byte main slot, then a spare byte where AC 63 and the EOB's zero land), else
 // int16_t x 64
 constexpr int kStageCompact = 80;
-template <class TT, class ST, int STRIDE>
-struct LdsWriteT {
+// (compact variant) the packed entry every lane of a hinted image started from (HintHdr), for its predecessor's proof
+template <bool KEEP>
+struct LdsKeptEntries {};
+template <>
+struct LdsKeptEntries<true> {
+  uint4 ent[kEntThreads];
+};
+template <class TT, class ST, int STRIDE, bool KEEP = false>
+struct LdsWriteT : LdsKeptEntries<KEEP> {
   unsigned long long t0, it;
   TT T;
   alignas(16) ST stage[kEntThreads * STRIDE];
@@ -1377,9 +1384,26 @@ __device__ int load_write_tables(WriteTables& W, const EntTables* g, int32_t* tm
 // The write pass's proof of a stored entry state (entwrite_image, LB = 11): a lane that stopped at bit `pos`, MCU
 // block blk, after nblk blocks of its interval (which holds seg_blocks), with the rotated predictors (pc: the next
 // block's component, p0 / p1: the following ones in the MCU's component cycle; pk_c: BlkCtx::pc), against its
-// successor's entry N.  Out of line: inside the pass it cost the decode loop 8 VGPRs and a wave of occupancy.
-__device__ __attribute__((noinline)) bool entry_proved(const SubState& N, uint32_t pos, int blk, int nblk, int seg_blocks,
+// successor's entry N, in the record's packed form (HintHdr) as the successor left it in LDS: what it actually started
+// from.  Out of line: inside the pass it cost the decode loop 8 VGPRs and a wave of occupancy.
+struct PackedEntry {
+  uint32_t entry_p;
+  uint16_t entry_bz;
+  int32_t nblk_ex, dc_ex[kMaxComp];
+};
+__device__ __forceinline__ PackedEntry unpack_entry(const uint4& r) {
+  PackedEntry N;
+  N.entry_p = r.x;
+  N.entry_bz = (uint16_t)((r.y >> 24) << 8);
+  N.nblk_ex = (int32_t)(r.y & 0xFFFFFFu);
+  N.dc_ex[0] = (int32_t)(int16_t)(r.z & 0xFFFFu);
+  N.dc_ex[1] = (int32_t)(int16_t)(r.z >> 16);
+  N.dc_ex[2] = (int32_t)(int16_t)(r.w & 0xFFFFu);
+  return N;
+}
+__device__ __attribute__((noinline)) bool entry_proved(const uint4 packed, uint32_t pos, int blk, int nblk, int seg_blocks,
                                                        int pc, int p0, int p1, int ncomp, uint32_t pk_c, int bpm) {
+  const PackedEntry N = unpack_entry(packed);
   // (a lane that ran out of blocks stopped early, as the sync pass's did not: then every later lane of the
   // interval must start out of blocks too, and none of them stores anything)
   if (nblk >= seg_blocks) return N.nblk_ex >= seg_blocks;
@@ -1390,16 +1414,71 @@ __device__ __attribute__((noinline)) bool entry_proved(const SubState& N, uint32
     if (cn != cb) succ[cb] = cn;
   }
   const int ce = comp(blk), c1 = succ[ce], c2 = succ[c1];
-  return pos == N.entry_p && (uint32_t)blk == (uint32_t)(N.entry_bz >> 8) && nblk == N.nblk_ex && pc == N.dc_ex[ce] &&
-         (ncomp != 3 || (p0 == N.dc_ex[c1] && p1 == N.dc_ex[c2]));
+  auto dc = [&](int k) { return k == 0 ? N.dc_ex[0] : (k == 1 ? N.dc_ex[1] : N.dc_ex[2]); };
+  return pos == N.entry_p && (uint32_t)blk == (uint32_t)(N.entry_bz >> 8) && nblk == N.nblk_ex && pc == dc(ce) &&
+         (ncomp != 3 || (p0 == dc(c1) && p1 == dc(c2)));
+}
+
+// What a lane of a hinted image (ImgDesc::hinted == kHintHit: one group, nseg <= nsub <= kEntThreads) starts the
+// write pass from, built by the lane itself: its subsequence of the layout (sdsj_common.h sub_layout) and its
+// packed entry from the image's record `rec`, trusted for memory safety only (hint_entry_safe).  Every thread of
+// the workgroup calls it; tmp: 2 x kEntThreads ints of LDS (the interval counts' scan, then their exclusive
+// sums); kept[t]: the entry the lane starts from, for its predecessor's proof.  A lane whose entry is unsafe
+// decodes nothing (kHlUnsafe) and sends the image to the retry list.  Out of line: the pass's decode loop keeps
+// its registers.
+constexpr uint32_t kHlLast = 1u << 30, kHlUnsafe = 1u << 31;
+struct HintedLane {
+  uint4 ent;                        // HintHdr's packed form; an interval's first entry is exact by the layout
+  uint32_t end_bit, lim_bit, seg_fl;  // seg_fl: the interval | kHlLast (its last subsequence) | kHlUnsafe
+};
+__device__ __attribute__((noinline)) HintedLane hinted_lane(ImgDesc* d, uint8_t* scratch, const uint8_t* rec, int32_t* tmp,
+                                                            uint4* kept) {
+  const int t = threadIdx.x;
+  const int nseg = d->nseg, nsub = d->nsub;
+  const uint32_t SB = (uint32_t)d->sub_bits;
+  const SegView sv = seg_view(scratch + d->off_seg, nseg);
+  int32_t* off = tmp + kEntThreads;
+  if (nseg > 1) {  // (uniform)
+    const int cnt = t < nseg ? sub_count(sv.lo[t], sv.hi[t], SB) : 0;
+    int total;
+    off[t] = block_excl_scan<kEntThreads>(cnt, tmp, &total);
+    __syncthreads();
+  }
+  HintedLane H{};
+  if (t < nsub) {
+    const int s = nseg > 1 ? sub_interval(off, nseg, t) : 0;
+    const SubLayout lay = sub_layout(sv.lo[s], sv.hi[s], SB, s, t - (nseg > 1 ? off[s] : 0), t, nsub);
+    uint4 ent = make_uint4(lay.start_bit, 0, 0, 0);
+    if (!lay.first) {
+      // (one read: another lane's stream may rewrite the record while this pass runs, and the proof is against
+      // the values this lane starts from)
+      ent = *reinterpret_cast<const uint4*>(rec + sizeof(HintHdr) + 16 * t);
+      asm volatile("" : "+v"(ent.x), "+v"(ent.y), "+v"(ent.z), "+v"(ent.w));
+    }
+    const bool safe = hint_entry_safe(ent.x, ent.y, lay, d->bpm);
+    if (!safe) {
+      ent = make_uint4(lay.start_bit, 0, 0, 0);
+      d->hinted = kHintFailed;
+    }
+    kept[t] = ent;
+    H.ent = ent;
+    H.end_bit = lay.end_bit;
+    H.lim_bit = lay.lim_bit;
+    H.seg_fl = (uint32_t)s | (lay.last && safe ? kHlLast : 0u) | (safe ? 0u : kHlUnsafe);
+  }
+  if (nseg > 1) __syncthreads();  // (the sums are read before the caller clears the stage)
+  return H;
 }
 
 // CP: the variant that writes the compact coefficient format (sdsj_common.h coef_compact: LB = 11 images
 // outside latency mode); each variant skips the other's images.  A lane's images are all in latency mode or
 // none is (k_parse's `small`), so launch_entwrite launches one of the two.
+// hrecs / hidx (CP, or null): the entry-point store's records and the lane's record index by image (hint_rec_index).
+// A hinted image (ImgDesc::hinted == kHintHit: one group, at most kEntThreads subsequences) has no SubStates laid
+// out: every lane builds its own subsequence's layout and takes its entry from the packed record.
 template <int LB, bool CP>
 __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
-                               uint8_t* __restrict__ scratch) {
+                               uint8_t* __restrict__ scratch, const uint8_t* hrecs, const int32_t* __restrict__ hidx) {
   static_assert(!CP || LB == 11, "the compact format belongs to the 11-bit routes");
   ImgDesc* d = &descs[img];
   if (d->status != SDSJ_OK) return;
@@ -1407,12 +1486,22 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
   constexpr bool kCompact = CP;
   using ST = std::conditional_t<kCompact, int8_t, int16_t>;
   constexpr int kStride = kCompact ? kStageCompact : kStageStride;
-  __shared__ LdsWriteT<TT, ST, kStride> L;
+  __shared__ LdsWriteT<TT, ST, kStride, CP> L;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  // entry states from the store (k_enthint), proved below.  Only the compact variant meets them: the int16 one
+  // decodes latency-mode lanes, which the store never serves, and stays the code it was.  (Read before the first
+  // barrier: a lane of this workgroup may set kHintFailed after it, and the barriers below depend on the value.)
+  const bool hinted = CP && d->hinted == kHintHit;
   int ns;
   if constexpr (LB == 11) ns = load_write_tables(L.T, &tables[d->etab], reinterpret_cast<int32_t*>(L.stage));
   else ns = load_tables<LB>(L.T, &tables[d->etab]);
   if (!variant_owns<LB>(ns) || coef_compact(*d) != kCompact) return;
+  HintedLane H{};  // (hinted) what this lane starts from
+  if constexpr (CP) {
+    // (the stage is the layout scan's scratch before it is cleared, as for load_write_tables)
+    if (hinted)
+      H = hinted_lane(d, scratch, hrecs + (int64_t)hidx[img] * kHintRowBytes, reinterpret_cast<int32_t*>(L.stage), L.ent);
+  }
   {
     uint4* z4 = reinterpret_cast<uint4*>(L.stage);
     for (int i = t; i < kEntThreads * kStride * (int)sizeof(ST) / 16; i += kEntThreads) z4[i] = make_uint4(0, 0, 0, 0);
@@ -1438,10 +1527,6 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
   const int my_base = t * kStride;
   int bad = 0;
   unsigned long long nsym = 0, witers = 0;
-  // entry states from the store (k_enthint), proved below.  Only the compact variant meets them: the int16 one
-  // decodes latency-mode lanes, which the store never serves, and stays the code it was
-  const bool hinted = CP && d->hinted == kHintHit;
-
   const int G = d->ent_groups, per = (nsub + G - 1) / G, j0 = grp * per, j1 = j0 + per < nsub ? j0 + per : nsub;
   for (int jb = j0; jb < j1; jb += kEntThreads) {  // uniform trip count for the whole workgroup
     const int j = jb + t;
@@ -1455,21 +1540,45 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
     bool last_of_seg = false, run = false;
     uint32_t stop_pos = 0, stop_blk = 0;
     if (active) {
-      const SubState& S = sub[j];
-      const int s = S.seg;
+      // the subsequence and its entry: from the SubState the sync pass verified, or (hinted) the lane's own
+      // layout and packed entry
+      int s, nblk_ex;
+      uint32_t entry_p, entry_bz;
+      if (hinted) {
+        const PackedEntry N = unpack_entry(H.ent);
+        s = (int)(H.seg_fl & ~(kHlLast | kHlUnsafe));
+        nblk_ex = N.nblk_ex;
+        p0 = N.dc_ex[0];
+        p1 = N.dc_ex[1];
+        p2 = N.dc_ex[2];
+        entry_p = N.entry_p;
+        entry_bz = N.entry_bz;
+        end_bit = H.end_bit;
+        lim = H.lim_bit;
+        last_of_seg = (H.seg_fl & kHlLast) != 0;  // (never an unsafe lane: it finishes no interval)
+      } else {
+        const SubState& S = sub[j];
+        s = S.seg;
+        nblk_ex = S.nblk_ex;
+        p0 = S.dc_ex[0];
+        p1 = S.dc_ex[1];
+        p2 = S.dc_ex[2];
+        entry_p = S.entry_p;
+        entry_bz = S.entry_bz;
+        end_bit = S.end_bit;
+        lim = S.lim_bit;
+        last_of_seg = (j + 1 == nsub) || sub[j + 1].first;
+      }
       const int g0 = s * blocks_per_seg;
       gend = g0 + blocks_per_seg;
       if (gend > (int)d->total_blocks) gend = (int)d->total_blocks;
-      g = g0 + S.nblk_ex;
-      p0 = S.dc_ex[0];
-      p1 = S.dc_ex[1];
-      p2 = S.dc_ex[2];
+      g = g0 + nblk_ex;
       // entries are block boundaries (z = 0): the speculative and the sync passes stop only there.  The
       // pass relies on that invariant (z starts at 0, no mid-block entry state); an entry that breaks it
       // fails the image (CORRUPT) instead of writing wrong coefficients
-      blk = S.entry_bz >> 8;
+      blk = (int)(entry_bz >> 8);
       z = 0;
-      if (S.entry_bz & 0xFF) d->status = SDSJ_CORRUPT;
+      if (entry_bz & 0xFF) d->status = SDSJ_CORRUPT;
       c = ctx_c(K, blk);
       if constexpr (LB == 11) {
         // predictors in component order from the entry block's component: pc = its own, p0 / p1 the
@@ -1492,15 +1601,13 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
         sac = ctx_ac(K, blk);
         pc = c == 0 ? p0 : (c == 1 ? p1 : p2);  // the current block's component predictor
       }
-      end_bit = S.end_bit;
       s_int = s;
-      lim = S.lim_bit;
-      last_of_seg = (j + 1 == nsub) || sub[j + 1].first;
-      bits_init(b, src, S.entry_p, S.lim_bit);
+      bits_init(b, src, entry_p, lim);
       // the interval's last subsequence decodes every remaining block; when its data runs out
       // (bits past lim, read as zeros) it finishes that MCU and stops: jdhuff.c insufficient_data
-      run = g < gend && (S.entry_bz & 0xFF) == 0 &&
+      run = g < gend && (entry_bz & 0xFF) == 0 &&
             (last_of_seg ? !(z == 0 && blk == 0 && b.pos > lim) : (b.pos < end_bit || z != 0));
+      if (H.seg_fl & kHlUnsafe) run = false;  // (hinted) an unsafe entry: the lane decodes nothing
       // one stop rule for both kinds: at a block boundary (z = 0) whose MCU position blk is in stop_blk
       // (the interval's last subsequence: MCU boundaries only) once pos >= stop_pos
       stop_pos = last_of_seg ? lim + 1 : end_bit;
@@ -1639,7 +1746,7 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
       if (b.pos > lim) sv.flag[s_int] |= kSegIns;          // ran out of data (JWRN_HIT_MARKER)
     }
     if constexpr (CP) {
-      // Entries from the store are proved here: this lane entered at sub[j].entry and stopped by the rule the
+      // Entries from the store are proved here: this lane entered at its kept entry and stopped by the rule the
       // speculative and sync passes use, so its exit is its successor's entry when its own entry was right.
       // An interval's first entry is exact by the layout; if every lane's exit equals the next entry -- bit
       // position, MCU block, block count, predictors -- every entry is the sequential decoder's by induction.
@@ -1649,7 +1756,7 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
         int jn = j + 1, g0 = s_int;
         asm volatile("" : "+v"(jn), "+v"(g0));
         g0 *= blocks_per_seg;
-        const bool ok = entry_proved(sub[jn], b.pos, blk, g - g0, gend - g0, pc, p0, p1, ncomp, K.pc, K.bpm);
+        const bool ok = entry_proved(L.ent[jn & (kEntThreads - 1)], b.pos, blk, g - g0, gend - g0, pc, p0, p1, ncomp, K.pc, K.bpm);
         if (!ok) d->hinted = kHintFailed;  // decoded again from scratch (k_hintreset and the passes after it)
       }
     }
@@ -1669,10 +1776,11 @@ __device__ void entwrite_image(int img, int grp, ImgDesc* __restrict__ descs, co
 
 
 template <int LB, int PHASE, int NTS = kSyncThreads, int NSPEC = kEntThreads, bool CP = false>
-__device__ __forceinline__ void ent_phase(int img, int grp, ImgDesc* descs, const EntTables* tables, uint8_t* scratch) {
+__device__ __forceinline__ void ent_phase(int img, int grp, ImgDesc* descs, const EntTables* tables, uint8_t* scratch,
+                                          const uint8_t* hrecs = nullptr, const int32_t* hidx = nullptr) {
   if (PHASE == 0) entspec_image<LB, NSPEC>(img, grp, descs, tables, scratch);
   else if (PHASE == 1) entsync_image<LB, NTS>(img, descs, tables, scratch);
-  else entwrite_image<LB, CP>(img, grp, descs, tables, scratch);
+  else entwrite_image<LB, CP>(img, grp, descs, tables, scratch, hrecs, hidx);
 }
 
 // The entropy kernels take images from a route list.  MODE 0: one workgroup per list entry (grid =
@@ -1684,7 +1792,8 @@ __device__ __forceinline__ void ent_phase(int img, int grp, ImgDesc* descs, cons
 // route's -- the images k_enthint left to the speculative and sync passes, or the retry list.
 template <int LB, int PHASE, int RT, int MODE, int NTS = kSyncThreads, int NSPEC = kEntThreads, bool CP = false>
 __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables, uint8_t* scratch, int32_t* routes,
-                                         int cap, const int32_t* alt = nullptr) {
+                                         int cap, const int32_t* alt = nullptr, const uint8_t* hrecs = nullptr,
+                                         const int32_t* hidx = nullptr) {
   if (MODE == 3) {  // (image, group) tasks (k_plan's group_tasks list); a capped grid strides over them
     const int nt = routes[kRtEnt11G];
     const int32_t* tasks = group_tasks(routes, cap);
@@ -1699,7 +1808,7 @@ __device__ __forceinline__ void ent_feed(ImgDesc* descs, const EntTables* tables
   const int32_t* list = MODE == 0 && alt ? alt + kHintListHdr : route_list(routes, cap, RT);
   if (MODE == 0) {  // one entry per workgroup at the full grid; a cold route's small grid strides (route_grid)
     for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
-      ent_phase<LB, PHASE, NTS, NSPEC, CP>(list[li], 0, descs, tables, scratch);
+      ent_phase<LB, PHASE, NTS, NSPEC, CP>(list[li], 0, descs, tables, scratch, hrecs, hidx);
       __syncthreads();  // LDS reuse by the next entry
     }
     return;
@@ -1749,12 +1858,14 @@ __global__ void __launch_bounds__(NTS) k_entsync(ImgDesc* __restrict__ descs, co
 
 // (The waves per SIMD each variant's LDS allows.  For CP the target binds: the proof of stored entries keeps two
 // predictors alive past the decode loop, and left to itself the compiler then takes 102 VGPRs instead of 94 -- 4
-// waves.  Held to 96 it spills three registers, reloaded on the flagged-DC path and between images only.)
+// waves.  Held to 96 it spills 11 registers, reloaded on the flagged-DC path, after the decode loop
+// and between images only; 31,872 B of LDS with the kept entries: still 5 workgroups per CU.)
 template <int LB, int RT, int MODE, bool CP>
 __global__ void __launch_bounds__(kEntThreads) __attribute__((amdgpu_waves_per_eu(CP ? 5 : (LB == 11 ? 4 : 3)))) k_entwrite(ImgDesc* __restrict__ descs, const EntTables* __restrict__ tables,
                                                           uint8_t* __restrict__ scratch, int32_t* __restrict__ routes,
-                                                          int cap, const int32_t* __restrict__ alt) {
-  ent_feed<LB, 2, RT, MODE, kSyncThreads, kEntThreads, CP>(descs, tables, scratch, routes, cap, alt);
+                                                          int cap, const int32_t* __restrict__ alt,
+                                                          const uint8_t* hrecs, const int32_t* __restrict__ hidx) {
+  ent_feed<LB, 2, RT, MODE, kSyncThreads, kEntThreads, CP>(descs, tables, scratch, routes, cap, alt, hrecs, hidx);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1931,32 +2042,37 @@ __device__ __forceinline__ unsigned long long hint_key_at(const unsigned long lo
 // An image the store serves: the single-group plan of the 11-bit route outside latency mode.
 __device__ __forceinline__ bool hint_eligible(const ImgDesc* d) { return !d->mh && !d->lat && d->ent_groups == 1; }
 
-// k_enthint, over the kRtEnt11 route (one workgroup per image): the subsequence layout, then the sample's record
-// by its address.  A record whose header equals the layout fills every subsequence's entry state as k_entsync
-// would leave it and marks the image hinted; every other image of the route goes to the lane's list for the
-// speculative and sync passes (lane[0] counts them).  What a record holds is trusted for nothing but memory
-// safety here (an entry inside its interval's bits, an MCU block of the image): k_entwrite proves the rest.
+// k_enthint, over the kRtEnt11 route (one wave per image): the subsequence count of the layout (sub_count summed
+// over the intervals), then the sample's record by its address.  A record whose header equals the layout marks
+// the image hinted and leaves its index where the write pass finds it (hint_rec_index): k_entwrite reads the
+// packed entries itself, trusts them for memory safety only (hint_entry_safe) and proves the rest.  Nothing is
+// laid out or unpacked here -- a hinted image's SubStates keep whatever the scratch held.  Every other image of
+// the route goes to the lane's list for the speculative and sync passes (lane[0] counts them).
 __global__ void __launch_bounds__(kEntThreads) k_enthint(ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
                                                          const int32_t* __restrict__ routes, int cap,
                                                          const uint8_t* blob, const int64_t* __restrict__ offsets,
                                                          const int32_t* __restrict__ lengths, HintStore hs,
                                                          int32_t* __restrict__ lane) {
-  __shared__ int32_t tmp[kEntThreads];
-  __shared__ long long slot_s;
-  const int t = threadIdx.x;
+  const int ln = threadIdx.x & 63;
   const int cnt = routes[kRtEnt11];
   const int32_t* list = route_list(routes, cap, kRtEnt11);
-  for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
+  int32_t* ridx = hint_rec_index(lane, cap);
+  constexpr int kWaves = kEntThreads / 64;
+  for (int li = blockIdx.x * kWaves + (threadIdx.x >> 6); li < cnt; li += gridDim.x * kWaves) {  // (wave-uniform)
     const int img = list[li];
     ImgDesc* d = &descs[img];
     if (d->status != SDSJ_OK) continue;
     bool hit = false;
-    if (hint_eligible(d)) {
-      const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
-      SubState* sub = reinterpret_cast<SubState*>(scratch + d->off_sub);
-      const int nsub = ent_layout<kEntThreads>(d, sv, sub, tmp);
-      const uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(blob + offsets[img]);
-      if (t == 0) {
+    const int nseg = d->nseg;
+    if (hint_eligible(d) && nseg <= kDecodeThreads) {  // (more intervals than lanes: more subsequences too)
+      const SegView sv = seg_view(scratch + d->off_seg, nseg);
+      const uint32_t SB = (uint32_t)d->sub_bits;
+      int sum = 0;
+      for (int s = ln; s < nseg; s += 64) sum += sub_count(sv.lo[s], sv.hi[s], SB);
+      for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+      const int nsub = sub_total(sum, d->nsub_cap);
+      if (ln == 0 && nsub <= kDecodeThreads) {
+        const uint64_t key = (uint64_t)reinterpret_cast<uintptr_t>(blob + offsets[img]);
         long long slot = -1;
         const int64_t slots = 2 * hs.rows;
         int64_t i = (int64_t)(hint_hash(key) % (uint64_t)slots);
@@ -1966,46 +2082,24 @@ __global__ void __launch_bounds__(kEntThreads) k_enthint(ImgDesc* __restrict__ d
           if (k == key || k == 0) break;
           i = i + 1 == slots ? 0 : i + 1;
         }
-        slot_s = slot;
-      }
-      __syncthreads();  // (also: the layout's stores are visible to every thread)
-      const long long slot = slot_s;
-      const HintHdr* h = reinterpret_cast<const HintHdr*>(hs.recs + (slot < 0 ? 0 : slot) * kHintRowBytes);
-      bool ok = slot >= 0 && nsub <= kDecodeThreads;
-      ok = ok && h->key == key && h->length == lengths[img] && h->nsub == nsub && h->entropy_len == d->entropy_len &&
-           h->ulen == d->ulen && h->sub_bits == d->sub_bits && h->nseg == d->nseg && h->bpm == d->bpm;
-      uint4 r = make_uint4(0, 0, 0, 0);
-      if (ok && t < nsub) {
-        r = reinterpret_cast<const uint4*>(h + 1)[t];
-        const SubState& S = sub[t];
-        // an entry is the first block boundary at or after start_bit: past the interval's data it can only
-        // finish one block of zero bits (64 symbols of at most 27 bits)
-        if (!S.first)
-          ok = r.x >= S.start_bit && (uint64_t)r.x <= (uint64_t)S.lim_bit + 2048u && (r.y >> 24) < (uint32_t)d->bpm;
-      }
-      hit = __syncthreads_and(ok);  // (a record another lane is writing may read differently per thread)
-      if (hit && t < nsub) {
-        SubState& S = sub[t];
-        const bool f = S.first;  // exact by the layout: the interval's first bit, block 0, nothing before it
-        S.entry_p = f ? S.start_bit : r.x;
-        S.entry_bz = f ? (uint16_t)0 : (uint16_t)((r.y >> 24) << 8);
-        S.nblk_ex = f ? 0 : (int32_t)(r.y & 0xFFFFFFu);
-        S.dc_ex[0] = f ? 0 : (int32_t)(int16_t)(r.z & 0xFFFFu);
-        S.dc_ex[1] = f ? 0 : (int32_t)(int16_t)(r.z >> 16);
-        S.dc_ex[2] = f ? 0 : (int32_t)(int16_t)(r.w & 0xFFFFu);
-      }
-      if (hit && t == 0) {
-        d->nsub = nsub;
-        d->sync_rounds = h->sync_rounds;
-        d->pad0 = h->pad0;
-        d->hinted = kHintHit;
+        if (slot >= 0 && slot < hs.rows) {
+          const HintHdr* h = reinterpret_cast<const HintHdr*>(hs.recs + slot * kHintRowBytes);
+          hit = h->key == key && h->length == lengths[img] && h->nsub == nsub && h->entropy_len == d->entropy_len &&
+                h->ulen == d->ulen && h->sub_bits == d->sub_bits && h->nseg == nseg && h->bpm == d->bpm;
+          if (hit) {
+            d->nsub = nsub;
+            d->sync_rounds = h->sync_rounds;
+            d->pad0 = h->pad0;
+            d->hinted = kHintHit;
+            ridx[img] = (int32_t)slot;
+          }
+        }
       }
     }
-    if (!hit && t == 0) {
+    if (!hit && ln == 0) {
       const int k = atomicAdd(&lane[0], 1);
       if (k < cap) lane[kHintListHdr + k] = img;
     }
-    __syncthreads();  // LDS reuse by the next entry
   }
 }
 
@@ -2013,52 +2107,73 @@ __global__ void __launch_bounds__(kEntThreads) k_enthint(ImgDesc* __restrict__ d
 // entries failed its verification go to the lane's retry list, back in the state k_unstuff left them -- that
 // pass's last lanes may have set vend and kSegIns from wrong entries.  (Their coefficient blocks need nothing:
 // the retry stores every block up to vend again, a flagged one zeroes its hi slot first, and the dc / hi entries
-// of unflagged blocks are never read.)
+// of unflagged blocks are never read.)  It also counts the proved hits (one atomic per workgroup) and lists every
+// other eligible image for k_hintstore (slist, counted in retry[kHintStoreCnt]): none in the steady state.
 __global__ void __launch_bounds__(kEntThreads) k_hintreset(const ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
                                                            const int32_t* __restrict__ routes, int cap,
-                                                           int32_t* __restrict__ retry) {
+                                                           int32_t* __restrict__ retry, int32_t* __restrict__ slist,
+                                                           unsigned long long* __restrict__ ctr) {
+  __shared__ unsigned int hits_s;
+  if (threadIdx.x == 0) hits_s = 0;
+  __syncthreads();
   const int cnt = routes[kRtEnt11];
   const int32_t* list = route_list(routes, cap, kRtEnt11);
-  for (int li = blockIdx.x * kEntThreads + threadIdx.x; li < cnt; li += gridDim.x * kEntThreads) {
-    const int img = list[li];
+  unsigned int n_hit = 0;
+  for (int l0 = blockIdx.x * kEntThreads; l0 < cnt; l0 += gridDim.x * kEntThreads) {  // (uniform trip count)
+    const int li = l0 + (int)threadIdx.x;
+    const int img = li < cnt ? list[li] : 0;
     const ImgDesc* d = &descs[img];
-    if (d->status != SDSJ_OK || d->hinted != kHintFailed) continue;
-    const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
-    const int64_t bps = d->restart_interval ? (int64_t)d->restart_interval * d->bpm : d->total_blocks;
-    for (int k = 0; k < d->nseg; k++) {
-      const int64_t ge = (int64_t)(k + 1) * bps;
-      sv.vend[k] = (int32_t)(ge < d->total_blocks ? ge : d->total_blocks);
-      sv.flag[k] &= ~kSegIns;
+    const bool served = li < cnt && d->status == SDSJ_OK && hint_eligible(d);
+    const bool hit = served && d->hinted == kHintHit;
+    n_hit += hit ? 1u : 0u;
+    // the images k_hintstore takes: one atomic per wave
+    const bool st = served && !hit;
+    const uint64_t m = __builtin_amdgcn_ballot_w64(st);
+    if (m) {
+      const int first = __builtin_ctzll(m);
+      const int idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+      int k0 = 0;
+      if ((int)(threadIdx.x & 63) == first) k0 = atomicAdd(&retry[kHintStoreCnt], __popcll(m));
+      k0 = __shfl(k0, first, 64);
+      if (st && k0 + idx < cap) slist[k0 + idx] = img;
     }
-    const int k = atomicAdd(&retry[0], 1);
-    if (k < cap) retry[kHintListHdr + k] = img;
+    if (served && d->hinted == kHintFailed) {
+      const SegView sv = seg_view(scratch + d->off_seg, d->nseg);
+      const int64_t bps = d->restart_interval ? (int64_t)d->restart_interval * d->bpm : d->total_blocks;
+      for (int k = 0; k < d->nseg; k++) {
+        const int64_t ge = (int64_t)(k + 1) * bps;
+        sv.vend[k] = (int32_t)(ge < d->total_blocks ? ge : d->total_blocks);
+        sv.flag[k] &= ~kSegIns;
+      }
+      const int k = atomicAdd(&retry[0], 1);
+      if (k < cap) retry[kHintListHdr + k] = img;
+    }
   }
+  if (n_hit) atomicAdd(&hits_s, n_hit);
+  __syncthreads();
+  if (threadIdx.x == 0 && hits_s) atomicAdd(&ctr[SDSJ_HINT_CTR_HITS], (unsigned long long)hits_s);
 }
 
-// k_hintstore, over the kRtEnt11 route after the write pass and its retry (a small grid strides over the list):
-// counts the images whose records were proved (hits), and records the verified entry states of every other
-// eligible image that decoded -- a miss, or a failed verification, whose row the fresh result overwrites.  An
+// k_hintstore, after the write pass and its retry (a small grid strides over the list k_hintreset made: the
+// eligible images that decoded without a proved hit, none in the steady state): records the verified entry
+// states of each -- a miss, or a failed verification, whose row the fresh result overwrites.  An
 // image whose values do not fit the packed entries (sdsj_common.h HintHdr), or whose key finds no slot within
-// kHintProbes or no record left, is not recorded.  ctr: SDSJ_HINT_CTR_*.
+// kHintProbes or no record left, is not recorded.  ctr: SDSJ_HINT_CTR_* (the hits: k_hintreset).
 __global__ void __launch_bounds__(kEntThreads) k_hintstore(const ImgDesc* __restrict__ descs,
                                                            const uint8_t* __restrict__ scratch,
-                                                           const int32_t* __restrict__ routes, int cap, const uint8_t* blob,
+                                                           const int32_t* __restrict__ retry,
+                                                           const int32_t* __restrict__ slist, int cap, const uint8_t* blob,
                                                            const int64_t* __restrict__ offsets,
                                                            const int32_t* __restrict__ lengths, HintStore hs,
                                                            unsigned long long* __restrict__ ctr) {
   __shared__ long long slot_s;
   const int t = threadIdx.x;
-  const int cnt = routes[kRtEnt11];
-  const int32_t* list = route_list(routes, cap, kRtEnt11);
-  unsigned int n_hit = 0, n_miss = 0, n_fail = 0, n_stored = 0;  // (thread 0's)
+  const int cnt = retry[kHintStoreCnt] < cap ? retry[kHintStoreCnt] : cap;
+  unsigned int n_miss = 0, n_fail = 0, n_stored = 0;  // (thread 0's)
   for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
-    const int img = list[li];
+    const int img = slist[li];
     const ImgDesc* d = &descs[img];
-    if (d->status != SDSJ_OK || !hint_eligible(d)) continue;
-    if (d->hinted == kHintHit) {
-      n_hit++;
-      continue;
-    }
+    if (d->status != SDSJ_OK) continue;
     if (d->hinted == kHintFailed) n_fail++;
     else n_miss++;
     const int nsub = d->nsub;
@@ -2123,7 +2238,6 @@ __global__ void __launch_bounds__(kEntThreads) k_hintstore(const ImgDesc* __rest
     __syncthreads();  // LDS reuse by the next entry
   }
   if (t == 0) {
-    if (n_hit) atomicAdd(&ctr[SDSJ_HINT_CTR_HITS], (unsigned long long)n_hit);
     if (n_miss) atomicAdd(&ctr[SDSJ_HINT_CTR_MISSES], (unsigned long long)n_miss);
     if (n_fail) atomicAdd(&ctr[SDSJ_HINT_CTR_VERIFY_FAILED], (unsigned long long)n_fail);
     if (n_stored) atomicAdd(&ctr[SDSJ_HINT_CTR_STORED], (unsigned long long)n_stored);
@@ -2155,7 +2269,9 @@ hipError_t launch_entspec(int n, ImgDesc* descs, const ImgTables* specs, void* e
       if (hipMemsetAsync(hl->lane, 0, sizeof(int32_t) * kHintListHdr, s) != hipSuccess ||
           hipMemsetAsync(hint_retry_list(hl->lane, cap), 0, sizeof(int32_t) * kHintListHdr, s) != hipSuccess)
         return hipGetLastError();
-      hipLaunchKernelGGL(k_enthint, dim3(route_grid(hint, kRtEnt11, g)), dim3(kEntThreads), 0, s, descs, scratch, routes, cap,
+      // (a wave per image; the retry list's header also counts k_hintstore's list)
+      hipLaunchKernelGGL(k_enthint, dim3(route_grid(hint, kRtEnt11, (g + kEntThreads / 64 - 1) / (kEntThreads / 64))),
+                         dim3(kEntThreads), 0, s, descs, scratch, routes, cap,
                          hl->blob, hl->offsets, hl->lengths, hl->store, hl->lane);
     }
     hipLaunchKernelGGL((k_entspec<11, kRtEnt11, 0, kSpecThreads>), dim3(hint_grid(hl, hint, route_grid(hint, kRtEnt11, g))),
@@ -2203,36 +2319,42 @@ hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scr
   const int g = n;  // one workgroup per image on the main route
   const EntTables* tables = static_cast<const EntTables*>(etab);
   const int32_t* no_alt = nullptr;
+  const uint8_t* no_recs = nullptr;
+  const int32_t* no_idx = nullptr;
   const int gs = g < 256 ? g : 256;
   // (latency-mode lanes keep the int16 coefficient format: coef_compact)
   if (route_on(rm, kRtEnt11)) {
     const dim3 grid(route_grid(hint, kRtEnt11, g));
     int32_t* retry = hl ? hint_retry_list(hl->lane, cap) : nullptr;
-    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
-    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
+    // (the compact variant reads a hinted image's entries from the store's records itself)
+    const uint8_t* hrecs = hl ? hl->store.recs : nullptr;
+    const int32_t* hidx = hl ? hint_rec_index(hl->lane, cap) : nullptr;
+    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt, no_recs, no_idx);
+    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt, hrecs, hidx);
     if (hl) {
       // the images whose stored entries the write pass refuted (none unless samples changed in place): the
       // ordinary passes over the retry list, from the state the refuted pass found (k_hintreset), then the
       // records of everything that decoded without a proved hit
       const dim3 rg(g < kHintColdGrid ? g : kHintColdGrid);
       hipLaunchKernelGGL(k_hintreset, dim3((g + kEntThreads - 1) / kEntThreads), dim3(kEntThreads), 0, s, descs, scratch, routes,
-                         cap, retry);
+                         cap, retry, hint_store_list(hl->lane, cap), hl->ctr);
       hipLaunchKernelGGL((k_entspec<11, kRtEnt11, 0, kSpecThreads>), rg, dim3(kSpecThreads), 0, s, descs, tables, scratch, routes, cap, retry);
       hipLaunchKernelGGL((k_entsync<11, kRtEnt11, 0, kSyncThreads>), rg, dim3(kSyncThreads), 0, s, descs, tables, scratch, routes, cap, retry);
-      if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), rg, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, retry);
-      else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), rg, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, retry);
-      hipLaunchKernelGGL(k_hintstore, dim3(g < 256 ? g : 256), dim3(kEntThreads), 0, s, descs, scratch, routes, cap, hl->blob,
+      if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, false>), rg, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, retry, no_recs, no_idx);
+      else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11, 0, true>), rg, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, retry, no_recs, no_idx);
+      hipLaunchKernelGGL(k_hintstore, dim3(g < 256 ? g : 256), dim3(kEntThreads), 0, s, descs, scratch, retry,
+                         hint_store_list(hl->lane, cap), cap, hl->blob,
                          hl->offsets, hl->lengths, hl->store, hl->ctr);
     }
   }
   if (route_on(rm, kRtEnt11M)) {
     const dim3 grid(route_grid(hint, kRtEnt11M, task_grid(n)));
-    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
-    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt);
+    if (small) hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, false>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt, no_recs, no_idx);
+    else hipLaunchKernelGGL((k_entwrite<11, kRtEnt11M, 3, true>), grid, dim3(kEntThreads), 0, s, descs, tables, scratch, routes, cap, no_alt, no_recs, no_idx);
   }
   if (route_on(rm, kRtEnt10))
     hipLaunchKernelGGL((k_entwrite<10, kRtEnt10, 1, false>), dim3(route_grid(hint, kRtEnt10, gs)), dim3(kEntThreads), 0, s, descs,
-                       tables, scratch, routes, cap, no_alt);
+                       tables, scratch, routes, cap, no_alt, no_recs, no_idx);
   return hipGetLastError();
 }
 
