@@ -40,7 +40,7 @@ extern "C" {
 /* status codes (per call and per sample) */
 #define SDSJ_OK 0
 #define SDSJ_EINVAL (-1)      /* bad argument */
-#define SDSJ_UNSUPPORTED (-2) /* valid JPEG the MI355X path does not decode (arithmetic, 12-bit, CMYK, ...) */
+#define SDSJ_UNSUPPORTED (-2) /* valid JPEG the MI355X path does not decode (arithmetic, 12-bit, CMYK without SDSJ_FORMAT_JPEG_CMYK, ...) */
 #define SDSJ_CORRUPT (-3)     /* malformed / truncated stream (PIL raises OSError) */
 #define SDSJ_ENOMEM (-4)      /* allocation failed */
 #define SDSJ_EHIP (-5)        /* HIP runtime error (see sdsj_last_error) */
@@ -62,8 +62,9 @@ extern "C" {
 
 typedef struct sdsj_info {
     int32_t width, height; /* image size (PIL Image.size order: width, height) */
-    int32_t ncomp;         /* 1 (grayscale) or 3 (YCbCr; RGB-coded under SDSJ_FORMAT_JPEG_EXT) */
-    int32_t h_samp[3], v_samp[3];
+    int32_t ncomp;         /* 1 (grayscale), 3 (YCbCr; RGB-coded under SDSJ_FORMAT_JPEG_EXT) or, under
+                              SDSJ_FORMAT_JPEG_CMYK, 4 (CMYK / YCCK) */
+    int32_t h_samp[3], v_samp[3]; /* (of a four-component file: its first three components) */
     int32_t restart_interval;
     int32_t supported; /* 1 if the MI355X path decodes it */
     int64_t entropy_offset;
@@ -91,7 +92,7 @@ int sdsj_abi_version(void);
 int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out);
 
 /* The same for an engine whose format mask is `formats` (it must have SDSJ_FORMAT_JPEG): with
- * SDSJ_FORMAT_JPEG_EXT or SDSJ_FORMAT_JPEG_SCANS (below) the files those bits admit are `supported`; without
+ * SDSJ_FORMAT_JPEG_EXT, SDSJ_FORMAT_JPEG_SCANS or SDSJ_FORMAT_JPEG_CMYK (below) the files those bits admit are `supported`; without
  * them the result is sdsj_probe's. */
 int sdsj_probe_formats(const uint8_t* jpg, size_t n, int formats, sdsj_info* out);
 
@@ -130,8 +131,8 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * other ratio by replication, int_upsample), and RGB-coded files -- those libjpeg's
  * default_decompress_parms takes as JCS_RGB: no JFIF marker and an Adobe marker with transform 0, or
  * neither marker and the component ids 'R', 'G', 'B' -- whose planes are stored as R, G, B without a
- * colour transform.  Fractional ratios, four components (CMYK / YCCK), arithmetic and 12-bit files stay
- * SDSJ_UNSUPPORTED.  Without the bit nothing changes: those files report SDSJ_UNSUPPORTED.
+ * colour transform.  Fractional ratios, four components (CMYK / YCCK: SDSJ_FORMAT_JPEG_CMYK), arithmetic and
+ * 12-bit files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: those files report SDSJ_UNSUPPORTED.
  *
  * SDSJ_FORMAT_JPEG_SCANS (valid only together with SDSJ_FORMAT_JPEG, SDSJ_EINVAL otherwise; it combines freely
  * with SDSJ_FORMAT_JPEG_EXT and the PNG bits) accepts multi-scan sequential files: 8-bit SOF0 / SOF1 frames of
@@ -144,6 +145,21 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * A file that ends at EOI before every component was coded decodes, the missing components from zero
  * coefficients, as in PIL.  Samplings with ratios of 3 and 4 and RGB-coded files need SDSJ_FORMAT_JPEG_EXT as
  * well.  Without the bit nothing changes: multi-scan sequential files report SDSJ_UNSUPPORTED.
+ *
+ * SDSJ_FORMAT_JPEG_CMYK (valid only together with SDSJ_FORMAT_JPEG, SDSJ_EINVAL otherwise; it combines freely
+ * with every other bit) accepts four-component files: 8-bit sequential (SOF0 / SOF1) Huffman frames of four
+ * components, giving the pixels of PIL.Image.open(...).convert("RGB").  The colour space is libjpeg's
+ * default_decompress_parms choice -- an Adobe marker with transform 0, or no Adobe marker: CMYK; an Adobe marker
+ * with any other transform: YCCK, whose first three planes are converted as ycck_cmyk_convert does; a JFIF
+ * marker plays no part and the component ids are free -- and the samples are taken inverted, as Pillow takes
+ * every four-component JPEG (Adobe's convention), then through Pillow's CMYK -> RGB.  Sampling factors are as
+ * for three components: ratios of 1 and 2 with this bit alone (a subsampled first component, and a subsampled
+ * K, included), ratios of 3 and 4 with SDSJ_FORMAT_JPEG_EXT as well; fractional ratios and more than 10 blocks
+ * per MCU stay SDSJ_UNSUPPORTED / SDSJ_CORRUPT as before.  One interleaved scan of all four components decodes
+ * with this bit alone; components that arrive in several scans need SDSJ_FORMAT_JPEG_SCANS as well and follow
+ * its rules.  Restart intervals are supported.  Progressive (SOF2), arithmetic-coded and 12-bit four-component
+ * files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: a four-component file reports
+ * SDSJ_UNSUPPORTED on every entry point.
  *
  * SDSJ_FORMAT_GIF is a third base format (valid alone or with any other bit): GIF87a / GIF89a, the first
  * frame on the logical screen, giving the pixels of PIL.Image.open(...).convert("RGB") -- the local colour
@@ -165,6 +181,7 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 #define SDSJ_FORMAT_JPEG_EXT 64
 #define SDSJ_FORMAT_JPEG_SCANS 128
 #define SDSJ_FORMAT_GIF 256 /* (bits 8 and 32 are not formats: SDSJ_EINVAL) */
+#define SDSJ_FORMAT_JPEG_CMYK 512
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -273,7 +290,7 @@ int sdsj_resize_frames_device(sdsj_engine* eng, int n, const uint8_t* d_frames, 
  * and copies up to `cap` counters (index = SDSJ_CTR_*); `reset` != 0 zeroes them afterwards. */
 #define SDSJ_CTR_IMAGES 0      /* JPEG samples submitted */
 #define SDSJ_CTR_OK 1          /* samples (images or frames) decoded / resized */
-#define SDSJ_CTR_UNSUPPORTED 2 /* valid images this path does not decode (PNG, WebP, arithmetic, 12-bit, CMYK...) */
+#define SDSJ_CTR_UNSUPPORTED 2 /* valid images this path does not decode (PNG, WebP, arithmetic, 12-bit, CMYK without its bit...) */
 #define SDSJ_CTR_CORRUPT 3     /* malformed / truncated streams */
 #define SDSJ_CTR_CAPACITY 4    /* samples that did not fit the scratch */
 #define SDSJ_CTR_OTHER 5       /* other per-sample errors (unreadable files) */

@@ -5,9 +5,11 @@
 // 8-bit sequential with one interleaved scan holding every component, SOF2 progressive -- whose
 // scans k_prog parses --, Huffman coding, optional DRI): the decoder Pillow calls from
 // sds/transforms/functional.py:100.  Everything else is reported as SDSJ_UNSUPPORTED (non-JPEG
-// input, lossless, arithmetic, 12-bit, CMYK; RGB-coded files and upsampling ratios above 2 too,
+// input, lossless, arithmetic, 12-bit; RGB-coded files and upsampling ratios above 2 too,
 // unless the engine's mask has SDSJ_FORMAT_JPEG_EXT: setup_geometry; multi-scan sequential files
-// too, unless it has SDSJ_FORMAT_JPEG_SCANS: parse_headers hands their scans to k_scans).
+// too, unless it has SDSJ_FORMAT_JPEG_SCANS: parse_headers hands their scans to k_scans; and
+// four-component sequential files -- CMYK / YCCK --, unless it has SDSJ_FORMAT_JPEG_CMYK: k_scans
+// decodes those as well, single-scan ones included).
 #pragma once
 #include <stdint.h>
 
@@ -139,8 +141,18 @@ struct CompDesc {
   int64_t plane_off;  // byte offset of this plane inside the image's plane area
 };
 
+// The fourth component of a CMYK / YCCK image (SDSJ_FORMAT_JPEG_CMYK), packed: ImgDesc keeps kMaxComp full
+// CompDesc entries and its pinned size, and this record lies over PNG fields a JPEG never uses (ImgDesc's
+// last union).  rh, rv and pitch are derived (comp_of); a plane offset stays below 2^30 (total_blocks < 2^24).
+struct CompRec {
+  uint8_t id, h, v, tq, td, ta, pad[2];
+  int32_t dw, dh, bw, bh;
+  int32_t plane_off;
+};
+static_assert(sizeof(CompRec) == 28, "the record covers png_ctype .. png_idat_pos exactly");
+
 enum GeoMode : int32_t { kGeoResize = 0, kGeoIdentity = 1, kGeoZeros = 2 };
-constexpr int32_t kScansSequential = 2;  // ImgDesc::progressive of a multi-scan sequential file (1: SOF2)
+constexpr int32_t kScansSequential = 2;  // ImgDesc::progressive of a file k_scans walks: multi-scan sequential, or four components (1: SOF2)
 
 struct ImgDesc {
   int32_t status;
@@ -203,7 +215,8 @@ struct ImgDesc {
   int32_t ent_groups;  // workgroups sharing the image's subsequences in the spec / write passes
   // progressive JPEG (SOF2): every scan is decoded by k_prog from sos_pos (the first SOS segment's
   // length field) into the zeroed coefficient array; ProgTables at off_ptab hold its table state.
-  // kScansSequential (2): a multi-scan sequential file (SOF0 / SOF1, SDSJ_FORMAT_JPEG_SCANS), walked
+  // kScansSequential (2): a multi-scan sequential file (SOF0 / SOF1, SDSJ_FORMAT_JPEG_SCANS) or a sequential
+  // file of four components (SDSJ_FORMAT_JPEG_CMYK), walked
   // from sos_pos the same way by k_scans -- everything that asks "progressive != 0" (no unstuffed
   // stream, int16 coefficient blocks, tables checked per scan) holds for it as it stands
   int32_t progressive;
@@ -238,12 +251,47 @@ struct ImgDesc {
   // from the IDAT chain at png_idat_pos, k_png_unfilter / k_png_unfilter_ext write the RGB rows at
   // off_rgb.  Bit depth and interlace travel in png_depth_lace (the struct's size and offsets are pinned).
   // png == 2 (kGifSample): a GIF sample (sdsj_gif.h gif_fill_desc says what each field carries then).
-  int32_t png;
-  int32_t png_ctype, png_bpp, png_plte_n;  // colour type, filter unit (bytes per pixel, 1 below depth 8), PLTE entries
-  int64_t png_plte_pos, png_idat_pos;      // relative to the sample's first byte
-  int64_t png_raw;
-  int64_t off_png;
+  // png == 0 and ncomp == 4: a CMYK / YCCK JPEG (SDSJ_FORMAT_JPEG_CMYK), whose fourth component is comp3 --
+  // read through comp_of / comp_id_of, written through put_comp.
+  union {
+    struct {
+      int32_t png;
+      int32_t png_ctype, png_bpp, png_plte_n;  // colour type, filter unit (bytes per pixel, 1 below depth 8), PLTE entries
+      int64_t png_plte_pos, png_idat_pos;      // relative to the sample's first byte
+      int64_t png_raw;
+      int64_t off_png;
+    };
+    struct {
+      int32_t png_is_zero;  // (png itself)
+      CompRec comp3;
+    };
+  };
 };
+
+// Component c = 0..3 of an image, by value: the descriptor's own entry, or the fourth component of a CMYK /
+// YCCK image unpacked from its record.
+SDSJ_HD inline CompDesc comp_of(const ImgDesc& d, int c) {
+  if (c < kMaxComp) return d.comp[c];
+  const CompRec& r = d.comp3;
+  CompDesc o;
+  o.h = r.h, o.v = r.v, o.tq = r.tq, o.td = r.td, o.ta = r.ta;
+  o.rh = d.hmax / (r.h ? r.h : 1), o.rv = d.vmax / (r.v ? r.v : 1);
+  o.dw = r.dw, o.dh = r.dh, o.bw = r.bw, o.bh = r.bh;
+  o.pitch = r.bw * 8;
+  o.plane_off = r.plane_off;
+  return o;
+}
+SDSJ_HD inline int comp_id_of(const ImgDesc& d, int c) { return c < kMaxComp ? d.comp_id[c] : d.comp3.id; }
+SDSJ_HD inline void put_comp(ImgDesc* d, int c, const CompDesc& v) {
+  if (c < kMaxComp) {
+    d->comp[c] = v;
+    return;
+  }
+  CompRec& r = d->comp3;
+  r.h = (uint8_t)v.h, r.v = (uint8_t)v.v, r.tq = (uint8_t)v.tq, r.td = (uint8_t)v.td, r.ta = (uint8_t)v.ta;
+  r.dw = v.dw, r.dh = v.dh, r.bw = v.bw, r.bh = v.bh;
+  r.plane_off = (int32_t)v.plane_off;
+}
 
 // One tile of k_unstuff's first pass: bytes it emits and split markers (RSTn, codes below SOF0) it
 // holds before the tile's end, where its data ends (first other marker or the end of the input; -1:
@@ -435,7 +483,7 @@ enum Route : int32_t {
   kRtEnt11G,                      // (count only) (image, group) tasks of the kRtEnt11M images: group_tasks()
   kRtUsSmall, kRtUsBig,           // unstuffing: k_us_serial / the tile-parallel passes (kUsSerialTiles)
   kRtPng,                         // PNG samples (k_png_inflate, k_png_unfilter); they resample through kRtUnfused
-  kRtScans,                       // multi-scan sequential images (k_scans; ImgDesc::progressive == kScansSequential)
+  kRtScans,                       // multi-scan sequential and four-component images (k_scans; ImgDesc::progressive == kScansSequential)
   kRtGif,                         // GIF samples (k_gif_lzw, k_gif_rgb; SDSJ_FORMAT_GIF); they resample through kRtUnfused
   kNumRoutes
 };
@@ -532,7 +580,8 @@ struct CopySink {
 // Parses markers up to the first SOS (jdmarker.c subset).  `rd(i)` returns byte i; `t` must be
 // non-null (no null checks: on the device it points into LDS).  Bulk table bytes go through `sink`.
 // formats: the engine's SDSJ_FORMAT_* mask; with SDSJ_FORMAT_JPEG_SCANS a sequential frame of three
-// components whose first SOS names fewer of them is accepted as kScansSequential.
+// components whose first SOS names fewer of them is accepted as kScansSequential; with SDSJ_FORMAT_JPEG_CMYK
+// a sequential frame of four components is, whatever its first SOS names (fewer than four: with both bits).
 template <class Reader, class Sink>
 SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, const Sink& sink,
                           int formats = SDSJ_FORMAT_JPEG) {
@@ -579,15 +628,19 @@ SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t,
         d->ncomp = rd(s + 5);
         if (d->height == 0 || d->width == 0) return SDSJ_UNSUPPORTED;  // DNL
         if (sl != 6 + 3 * d->ncomp) return SDSJ_CORRUPT;                // get_sof: JERR_BAD_LENGTH
-        if (d->ncomp != 1 && d->ncomp != 3) return SDSJ_UNSUPPORTED;
+        // (four components: sequential frames under SDSJ_FORMAT_JPEG_CMYK; k_prog knows three)
+        const bool four = d->ncomp == 4 && m != 0xC2 && (formats & SDSJ_FORMAT_JPEG_CMYK);
+        if (d->ncomp != 1 && d->ncomp != 3 && !four) return SDSJ_UNSUPPORTED;
         d->hmax = d->vmax = 1;
         for (int c = 0; c < d->ncomp; c++) {
-          CompDesc& cp = d->comp[c];
-          d->comp_id[c] = rd(s + 6 + 3 * c);
+          CompDesc cp = CompDesc();
           int hv = rd(s + 7 + 3 * c);
           cp.h = hv >> 4;
           cp.v = hv & 15;
           cp.tq = rd(s + 8 + 3 * c);
+          if (c < kMaxComp) d->comp_id[c] = rd(s + 6 + 3 * c);
+          else d->comp3.id = (uint8_t)rd(s + 6 + 3 * c);
+          put_comp(d, c, cp);
           if (cp.h < 1 || cp.h > 4 || cp.v < 1 || cp.v > 4 || cp.tq > 3) return SDSJ_CORRUPT;
           if (cp.h > d->hmax) d->hmax = cp.h;
           if (cp.v > d->vmax) d->vmax = cp.v;
@@ -657,7 +710,11 @@ SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t,
           d->entropy_len = n - d->entropy_off;
           return SDSJ_OK;
         }
-        if (ns < d->ncomp && d->ncomp == 3 && (formats & SDSJ_FORMAT_JPEG_SCANS)) {  // every scan is parsed by k_scans
+        // every scan is parsed by k_scans: a frame of three or four components whose first scan names fewer of
+        // them, and every four-component frame (the single interleaved scan of all four too: the speculative
+        // entropy kernels know three components)
+        if (d->ncomp == 4 && ns < 4 && !(formats & SDSJ_FORMAT_JPEG_SCANS)) return SDSJ_UNSUPPORTED;
+        if (d->ncomp == 4 || (ns < d->ncomp && d->ncomp == 3 && (formats & SDSJ_FORMAT_JPEG_SCANS))) {
           d->progressive = kScansSequential;
           d->sos_pos = i;
           d->entropy_off = i + len;
@@ -703,7 +760,10 @@ SDSJ_HD inline bool rgb_coded(const ImgDesc& d) {
 // fused kernels convert YCbCr and assume ratios of 1 or 2.
 SDSJ_HD inline bool jpeg_ext_image(const ImgDesc& d) {
   bool wide = false;
-  for (int c = 0; c < d.ncomp; c++) wide |= d.comp[c].rh > 2 || d.comp[c].rv > 2;
+  for (int c = 0; c < d.ncomp; c++) {
+    const CompDesc cd = comp_of(d, c);
+    wide |= cd.rh > 2 || cd.rv > 2;
+  }
   return wide || rgb_coded(d);
 }
 
@@ -714,14 +774,15 @@ SDSJ_HD inline int setup_geometry(ImgDesc* d, const ImgTables* t, int formats = 
   if (rgb_coded(*d) && !ext) return SDSJ_UNSUPPORTED;  // Adobe RGB, or 'R','G','B' component ids
   int bpm = 0;
   for (int c = 0; c < d->ncomp; c++) {
-    CompDesc& cp = d->comp[c];
+    CompDesc cp = comp_of(*d, c);
     if (d->hmax % cp.h || d->vmax % cp.v) return SDSJ_UNSUPPORTED;
     cp.rh = d->hmax / cp.h;
     cp.rv = d->vmax / cp.v;
     if ((cp.rh > 2 || cp.rv > 2) && !ext) return SDSJ_UNSUPPORTED;
     cp.dw = ceil_div(d->width * cp.h, d->hmax);
     cp.dh = ceil_div(d->height * cp.v, d->vmax);
-    if (d->progressive) continue;  // tables are checked per scan (k_prog)
+    put_comp(d, c, cp);
+    if (d->progressive) continue;  // tables are checked per scan (k_prog, k_scans)
     if (!t->qt_defined[cp.tq]) return SDSJ_CORRUPT;
     if (!t->dc_spec[cp.td].defined || !t->ac_spec[cp.ta].defined) return SDSJ_CORRUPT;
   }
@@ -739,10 +800,12 @@ SDSJ_HD inline int setup_geometry(ImgDesc* d, const ImgTables* t, int formats = 
     d->mcux = ceil_div(d->width, 8 * d->hmax);
     d->mcuy = ceil_div(d->height, 8 * d->vmax);
     for (int c = 0; c < d->ncomp; c++) {
-      d->comp[c].bw = d->mcux * d->comp[c].h;
-      d->comp[c].bh = d->mcuy * d->comp[c].v;
-      for (int v = 0; v < d->comp[c].v; v++)
-        for (int h = 0; h < d->comp[c].h; h++) {
+      CompDesc cp = comp_of(*d, c);
+      cp.bw = d->mcux * cp.h;
+      cp.bh = d->mcuy * cp.v;
+      put_comp(d, c, cp);
+      for (int v = 0; v < cp.v; v++)
+        for (int h = 0; h < cp.h; h++) {
           if (bpm >= kMaxBlocksPerMcu) return SDSJ_CORRUPT;
           d->blk_comp[bpm] = c;
           d->blk_dx[bpm] = h;
@@ -754,9 +817,10 @@ SDSJ_HD inline int setup_geometry(ImgDesc* d, const ImgTables* t, int formats = 
   }
   int64_t plane = 0;
   for (int c = 0; c < d->ncomp; c++) {
-    CompDesc& cp = d->comp[c];
+    CompDesc cp = comp_of(*d, c);
     cp.pitch = cp.bw * 8;
     cp.plane_off = plane;
+    put_comp(d, c, cp);
     plane += align_up((int64_t)cp.pitch * cp.bh * 8, 256);
   }
   d->total_blocks = (int64_t)d->mcux * d->mcuy * d->bpm;
@@ -811,9 +875,9 @@ SDSJ_HD inline int nearest_src(int in_size, int out_size, int xx) {
 // k_entwrite stores only these: the source rectangle [src_x0, src_x0 + src_w) x [src_y0, src_y1) in the
 // component's sampling, widened by one sample for the fancy upsampling's neighbours, as inclusive block
 // bounds.  False when the crop is empty (nothing is read).
-SDSJ_HD inline bool comp_block_rect(const ImgDesc& d, int c, int& bx0, int& bx1, int& by0, int& by1) {
+// (cd: the component itself -- comp_of for the fourth one of a CMYK / YCCK image)
+SDSJ_HD inline bool comp_block_rect(const ImgDesc& d, const CompDesc& cd, int& bx0, int& bx1, int& by0, int& by1) {
   const int x0 = d.src_x0, x1 = d.src_x0 + d.src_w, y0 = d.src_y0, y1 = d.src_y1;
-  const CompDesc& cd = d.comp[c];
   const int rh = d.ncomp == 1 ? 1 : d.hmax / cd.h, rv = d.ncomp == 1 ? 1 : d.vmax / cd.v;
   int cx0 = x0 / rh - 1, cx1 = (x1 - 1) / rh + 1, cy0 = y0 / rv - 1, cy1 = (y1 - 1) / rv + 1;
   cx0 = cx0 < 0 ? 0 : cx0;
@@ -825,6 +889,9 @@ SDSJ_HD inline bool comp_block_rect(const ImgDesc& d, int c, int& bx0, int& bx1,
   by0 = cy0 >> 3;
   by1 = cy1 >> 3;
   return x1 > x0 && y1 > y0 && d.geo != kGeoZeros;
+}
+SDSJ_HD inline bool comp_block_rect(const ImgDesc& d, int c, int& bx0, int& bx1, int& by0, int& by1) {
+  return comp_block_rect(d, d.comp[c], bx0, bx1, by0, by1);
 }
 
 SDSJ_HD inline double filter_support(int filter) {

@@ -242,7 +242,7 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   mark(3);
   // (after mark 3: the next lane may start while this lane's progressive images decode)
   SDSJ_HIP(e, launch_prog(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
-  if (e->formats & SDSJ_FORMAT_JPEG_SCANS)  // (counts under the progressive stage)
+  if (e->formats & (SDSJ_FORMAT_JPEG_SCANS | SDSJ_FORMAT_JPEG_CMYK))  // (counts under the progressive stage)
     SDSJ_HIP(e, launch_scans(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (evs) (void)hipEventRecord((*evs)[kPngEvent].get(), s);
   if (e->formats & SDSJ_FORMAT_GIF)  // (counts under "png_inflate")
@@ -260,8 +260,12 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   SDSJ_HIP(e, launch_entwrite(n, ln.descs, ln.etab, e->scratch.get(), ln.routes, cap, s, rm, hint, small, hl));
   mark(7);
   SDSJ_HIP(e, launch_idct(n, ln.descs, ln.tables, e->scratch.get(), s));
+  if (e->formats & SDSJ_FORMAT_JPEG_CMYK)  // (four-component images: k_idct<kMaxComp> leaves them to k_idct<4>)
+    SDSJ_HIP(e, launch_idct4(n, ln.descs, ln.tables, e->scratch.get(), s, rm));
   mark(8);
   SDSJ_HIP(e, launch_color(n, ln.descs, e->scratch.get(), ln.routes, cap, s, rm));
+  if (e->formats & SDSJ_FORMAT_JPEG_CMYK)  // (... and k_color to k_cmyk)
+    SDSJ_HIP(e, launch_cmyk(n, ln.descs, e->scratch.get(), ln.routes, cap, s, rm, hint));
   mark(9);
   SDSJ_HIP(e, launch_coeffs(n, ln.descs, op, e->scratch.get(), s));
   mark(10);
@@ -737,9 +741,9 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 }
 
 // A format mask names at least one of JPEG, PNG and GIF, nothing unknown, PNG_EXT and PNG_META (alone or
-// together) only with PNG, and JPEG_EXT and JPEG_SCANS (alone or together) only with JPEG.
+// together) only with PNG, and JPEG_EXT, JPEG_SCANS and JPEG_CMYK (in any combination) only with JPEG.
 static bool valid_formats(int mask) {
-  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS;
+  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS | SDSJ_FORMAT_JPEG_CMYK;
   const int base = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_GIF, all = base | sub | jsub;
   return (mask & base) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
          (!(mask & jsub) || (mask & SDSJ_FORMAT_JPEG));

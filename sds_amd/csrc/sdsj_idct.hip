@@ -2,6 +2,8 @@
 //
 // Stage map (reference behaviour each kernel reproduces, see DESIGN.md for the layout/rooflines):
 //   k_idct     dequant + ISLOW IDCT                jidctint.c jpeg_idct_islow
+//              (k_idct<kMaxComp>: every image but the four-component ones of SDSJ_FORMAT_JPEG_CMYK, which
+//               k_idct<4> takes when the engine's mask has that bit)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -81,6 +83,10 @@ __device__ __forceinline__ void dequant8(const uint32_t* m, const uint32_t* h, c
 #ifndef SDSJ_IDCT_WAVES
 #define SDSJ_IDCT_WAVES 4  // waves per SIMD the register budget targets (124 VGPRs at 4)
 #endif
+// NC: the components the instantiation holds.  k_idct<kMaxComp> is the kernel every mask launches and leaves
+// four-component images alone; k_idct<4> takes only those -- k_scans' images (int16 blocks, no cut restart
+// intervals), whose fourth component comes from comp_of -- and is launched only under SDSJ_FORMAT_JPEG_CMYK.
+template <int NC>
 __global__ void __launch_bounds__(kIdctThreads) __attribute__((amdgpu_waves_per_eu(SDSJ_IDCT_WAVES)))
 k_idct(int n, const ImgDesc* __restrict__ descs,
                                                        const ImgTables* __restrict__ tables,
@@ -89,22 +95,27 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
   if (img >= n) return;
   const ImgDesc* d = &descs[img];
   if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->png) return;
+  if (NC > kMaxComp ? d->ncomp != NC : d->ncomp > NC) return;
   int nwg = gridDim.x;  // this image's workgroups
   if (SDSJ_IDCT_GPW > 0 && gridDim.x == kIdctGridMax) {
     const int64_t want = ((int64_t)d->total_blocks / 8 + SDSJ_IDCT_GPW - 1) / SDSJ_IDCT_GPW;
     nwg = want < 1 ? 1 : (want > kIdctGridMax ? kIdctGridMax : (int)want);
     if ((int)blockIdx.x >= nwg) return;
   }
-  __shared__ alignas(16) int32_t qt[kMaxComp][64];
-  __shared__ int32_t binv[kMaxComp][16];  // (dy * 4 + dx) -> MCU block index b (jdcoefct order)
-  __shared__ int32_t gstart[kMaxComp + 1], ngx[kMaxComp], cbw[kMaxComp], ch_[kMaxComp], cv_[kMaxComp], cpitch[kMaxComp];
-  __shared__ int32_t cgx0[kMaxComp], cby0[kMaxComp];  // first 8-block group column / block row needed
-  __shared__ float rngx[kMaxComp], rch[kMaxComp], rcv[kMaxComp];  // reciprocals for the exact quotients below
-  __shared__ int64_t cplane[kMaxComp];
+  __shared__ alignas(16) int32_t qt[NC][64];
+  __shared__ int32_t binv[NC][16];  // (dy * 4 + dx) -> MCU block index b (jdcoefct order)
+  __shared__ int32_t gstart[NC + 1], ngx[NC], cbw[NC], ch_[NC], cv_[NC], cpitch[NC];
+  __shared__ int32_t cgx0[NC], cby0[NC];  // first 8-block group column / block row needed
+  __shared__ float rngx[NC], rch[NC], rcv[NC];  // reciprocals for the exact quotients below
+  __shared__ int64_t cplane[NC];
   const int t = threadIdx.x;
   const int ncomp = d->ncomp, bpm = d->bpm, mcux = d->mcux;
   // quantisation tables in zigzag order (the coefficient blocks' order)
-  for (int i = t; i < ncomp * 64; i += kIdctThreads) qt[i / 64][i % 64] = tables[img].qt[d->comp[i / 64].tq][natural_order(i % 64)];
+  if constexpr (NC > kMaxComp) {
+    for (int i = t; i < ncomp * 64; i += kIdctThreads) qt[i / 64][i % 64] = tables[img].qt[comp_of(*d, i / 64).tq][natural_order(i % 64)];
+  } else {
+    for (int i = t; i < ncomp * 64; i += kIdctThreads) qt[i / 64][i % 64] = tables[img].qt[d->comp[i / 64].tq][natural_order(i % 64)];
+  }
   if (t < bpm) binv[d->blk_comp[t]][d->blk_dy[t] * 4 + d->blk_dx[t]] = t;
   if (t == 0) {
     // only the blocks whose pixels the colour/resample passes read (comp_block_rect: the crop's source
@@ -113,9 +124,10 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
     // first needed block column instead: k_idct 4.70 -> 5.18 ms per 16,384, profiles/r05_ab.txt)
     int acc = 0;
     for (int c = 0; c < ncomp; c++) {
-      const CompDesc& cd = d->comp[c];
+      const CompDesc cd4 = NC > kMaxComp ? comp_of(*d, c) : CompDesc();
+      const CompDesc& cd = NC > kMaxComp ? cd4 : d->comp[c];
       int bx0, bx1, by0, by1;
-      const bool any = comp_block_rect(*d, c, bx0, bx1, by0, by1);
+      const bool any = comp_block_rect(*d, cd, bx0, bx1, by0, by1);
       gstart[c] = acc;
       cgx0[c] = bx0 >> 3;
       ngx[c] = (bx1 >> 3) - cgx0[c] + 1;
@@ -139,7 +151,7 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
   // (evaluated by every wave, on its scalar unit from the descriptor: the value stays in an SGPR and the format
   // branch below stays uniform.  Held in LDS instead, once per workgroup, the branch became a vector one and
   // k_idct went 15.6 -> 24.4 ms per 65,536)
-  const bool compact = coef_compact(*d);
+  const bool compact = NC > kMaxComp ? false : coef_compact(*d);
   const uint8_t* coef = scratch + d->off_coef;
   const int16_t* cdc = reinterpret_cast<const int16_t*>(coef + coef_dc_off(d->total_blocks));
   const uint8_t* chi = coef + coef_hi_off(d->total_blocks);
@@ -168,6 +180,7 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
   // block lb of group grp: component, block coordinates, decode-order index (g < 0: none)
   auto locate = [&](int grp, int& c, int& by, int& bx, int& g) {
     c = ncomp > 1 && grp >= gstart[1] ? (ncomp > 2 && grp >= gstart[2] ? 2 : 1) : 0;
+    if constexpr (NC > kMaxComp) c = grp >= gstart[kMaxComp] ? kMaxComp : c;
     const int local = grp - gstart[c];
     const int byl = qdiv(local, ngx[c], rngx[c]);
     by = cby0[c] + byl;
@@ -275,8 +288,14 @@ k_idct(int n, const ImgDesc* __restrict__ descs,
 // ------------------------------------------------------------------------------------------
 hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s) {
   // (a few images: more workgroups per image, for latency)
-  hipLaunchKernelGGL(k_idct, dim3(n <= kSmallBatch ? 8 * kIdctGrid : (SDSJ_IDCT_GPW > 0 ? kIdctGridMax : kIdctGrid), n), dim3(kIdctThreads), 0, s, n, descs,
+  hipLaunchKernelGGL(k_idct<kMaxComp>, dim3(n <= kSmallBatch ? 8 * kIdctGrid : (SDSJ_IDCT_GPW > 0 ? kIdctGridMax : kIdctGrid), n), dim3(kIdctThreads), 0, s, n, descs,
                      tables, scratch);
+  return hipGetLastError();
+}
+// (grid rows = the lane's images, as for k_idct: a row whose image has not four components exits at once)
+hipError_t launch_idct4(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s, uint64_t rm) {
+  if (!route_on(rm, kRtScans)) return hipSuccess;
+  hipLaunchKernelGGL(k_idct<4>, dim3(kIdctGrid, n), dim3(kIdctThreads), 0, s, n, descs, tables, scratch);
   return hipGetLastError();
 }
 

@@ -66,7 +66,8 @@ hipError_t launch_prog(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* 
 // k_prog_zero (sdsj_progressive.hip) over the images of route rt (kRtProg or kRtScans): their int16 coefficient arrays zeroed
 void launch_coef_zero(int rt, int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                       uint64_t hint);
-// multi-scan sequential images (route kRtScans; engines with SDSJ_FORMAT_JPEG_SCANS): zero their coefficients, then
+// multi-scan sequential images and four-component ones (route kRtScans; engines with SDSJ_FORMAT_JPEG_SCANS or
+// SDSJ_FORMAT_JPEG_CMYK): zero their coefficients, then
 // one wave per image decodes every scan (sdsj_scans.hip)
 hipError_t launch_scans(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
                         const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
@@ -96,6 +97,13 @@ hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scr
                            hipStream_t s, uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes, bool small = false,
                            const HintLane* hl = nullptr);
 hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s);
+// four-component images (CMYK / YCCK; engines with SDSJ_FORMAT_JPEG_CMYK), which k_idct<kMaxComp> and k_color skip:
+// k_idct<4> (sdsj_idct.hip) over the lane's images, k_cmyk (sdsj_unfused.hip) over route kRtScans' list; both take
+// only the images of four components
+hipError_t launch_idct4(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s,
+                        uint64_t rm = kAllRoutes);
+hipError_t launch_cmyk(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+                       uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
 hipError_t launch_color(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                         uint64_t rm = kAllRoutes);
 hipError_t launch_coeffs(int n, ImgDesc* descs, const sdsj_op& op, uint8_t* scratch, hipStream_t s);

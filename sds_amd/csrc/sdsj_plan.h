@@ -120,6 +120,9 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   // SDSJ_FORMAT_JPEG_EXT images (RGB-coded, or a ratio above 2): the unfused passes, whose k_color
   // restates every upsampling method and the missing colour transform
   else if (jpeg_ext_image(*d)) d->fused = 0;
+  // SDSJ_FORMAT_JPEG_CMYK images (four components): the unfused passes too, behind a colour kernel of their
+  // own (k_cmyk), which writes the RGB rows k_color writes for the others
+  else if (d->ncomp > kMaxComp) d->fused = 0;
   // specialised fused kernels (sdsj_resample420.hip): 4:2:0 (h2v2 fancy chroma), 4:2:2 (h2v1 fancy
   // chroma), 4:4:4 and grayscale, horizontal and vertical passes, odd tap counts 3..11; everything
   // else takes the generic k_resample
@@ -145,7 +148,8 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   // only the 11-bit entropy routes launch it (k_entspec_mh), so images of more than 4 table slots
   // (kRtEnt10) keep the ordinary speculative pass
   // (the table slots, counted once: they also choose the coefficient format; frames and PNGs have no scan)
-  const int slots = frames || png ? 2 * kMaxComp : huff_slots(*d);
+  // (a four-component image is walked by k_scans, which counts no slots: int16 blocks whatever they are)
+  const int slots = frames || png || d->ncomp > kMaxComp ? 2 * kMaxComp : huff_slots(*d);
   d->mh = (int8_t)(SDSJ_MH && d->lat && !d->progressive && d->restart_interval == 0 && d->bpm <= kMhMaxPhases &&
                    slots <= 4);
   d->hinted = 0;  // (k_enthint sets it)
@@ -187,7 +191,10 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   d->off_ptab = take(prog ? (int64_t)sizeof(ProgTables) : 0);
   d->off_coef = take(coef_bytes(*d, slots));
   int64_t planes = 0;
-  for (int c = 0; c < d->ncomp; c++) planes += align_up((int64_t)d->comp[c].pitch * d->comp[c].bh * 8, 256);
+  for (int c = 0; c < d->ncomp; c++) {
+    const CompDesc cd = comp_of(*d, c);
+    planes += align_up((int64_t)cd.pitch * cd.bh * 8, 256);
+  }
   d->off_planes = take(planes);
   d->off_rgb = take(d->fused || frames ? 0 : (int64_t)d->src_w * (d->src_y1 - d->src_y0) * 3);
   d->rgb_pitch = d->src_w;  // k_color packs the crop rows
@@ -209,7 +216,7 @@ SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
     *rr = d.geo == kGeoZeros ? -1 : kRtUnfused;
     return;
   }
-  const int ns = huff_slots(d);
+  const int ns = d.progressive ? 0 : huff_slots(d);  // (it chooses among the baseline entropy routes only)
   *ru = d.progressive ? -1 : (d.ntiles > kUsSerialTiles || d.lat ? kRtUsBig : kRtUsSmall);
   *re = d.progressive == kScansSequential ? kRtScans : d.progressive ? kRtProg : ns > 4 ? kRtEnt10 : (d.ent_groups > 1 ? kRtEnt11M : kRtEnt11);
   *rr = d.geo == kGeoZeros ? -1
@@ -227,7 +234,7 @@ SDSJ_HD int parse_sample(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t, 
 }
 
 // The host's side of what k_scans refuses while it walks the scans of a multi-scan sequential file
-// (ImgDesc::progressive == kScansSequential): a scan that is not a full sequential one or codes a
+// (ImgDesc::progressive == kScansSequential; every four-component file is one): a scan that is not a full sequential one or codes a
 // component again (SDSJ_UNSUPPORTED: libjpeg only warns and overlays the coefficients), a malformed SOS
 // and, in a scan without restart intervals, fill bytes before a stuffed zero (SDSJ_CORRUPT: k_scans'
 // fill_stuffed).  A marker walk, no entropy decoding: host planning and the probe run it, so that such a file is
@@ -245,7 +252,7 @@ inline int scans_check(const Reader& rd, int64_t n, const ImgDesc& d) {
     for (int q = 0; q < ns; q++) {
       const int cid = rd(pos + 3 + 2 * q);
       int c = 0;
-      while (c < d.ncomp && d.comp_id[c] != cid) c++;
+      while (c < d.ncomp && comp_id_of(d, c) != cid) c++;
       if (c == d.ncomp) return SDSJ_CORRUPT;
       if ((coded >> c) & 1) return SDSJ_UNSUPPORTED;
       coded |= 1 << c;

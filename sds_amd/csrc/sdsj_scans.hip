@@ -1,5 +1,6 @@
 // sdsj_scans.hip -- multi-scan sequential JPEG (SOF0 / SOF1 frames whose components arrive in more than one
-// scan) for the MI355X path, under SDSJ_FORMAT_JPEG_SCANS.
+// scan) for the MI355X path, under SDSJ_FORMAT_JPEG_SCANS, and every sequential frame of four components (CMYK /
+// YCCK, in one interleaved scan or several) under SDSJ_FORMAT_JPEG_CMYK.
 //
 // Restates libjpeg-turbo's sequential Huffman decoder as Pillow runs it on such a file: jdhuff.c decode_mcu (the
 // DC difference and the run/size AC symbols of every block of an MCU in one pass, no EOB runs, no successive
@@ -76,6 +77,7 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
   const int mcux = d->mcux, bpm = d->bpm, ncomp = d->ncomp;
   // first block of each component within an MCU
   const int boff1 = d->comp[0].h * d->comp[0].v, boff2 = boff1 + d->comp[1].h * d->comp[1].v;
+  const int boff3 = boff2 + d->comp[2].h * d->comp[2].v;  // (the fourth component of a CMYK / YCCK frame)
   int pos = (int)d->sos_pos;
   for (;;) {
     if (pos + 2 > n) return SDSJ_CORRUPT;
@@ -85,28 +87,30 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
     if (sl < 1) return SDSJ_CORRUPT;
     const int ns = s[0];
     if (ns < 1 || ns > 4 || sl != 2 * ns + 4) return SDSJ_CORRUPT;  // get_sos: JERR_BAD_LENGTH
-    if (ns > 3) return SDSJ_UNSUPPORTED;  // (a frame of three components: one of them would be coded twice)
+    if (ns > ncomp) return SDSJ_UNSUPPORTED;  // (a frame of three components: one of them would be coded twice)
     // (per-position arrays are indexed only from unrolled loops, so they stay in registers)
-    int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, sh[3] = {1, 1, 1}, sv[3] = {1, 1, 1}, sbo[3] = {0, 0, 0}, ldc[3] = {0, 0, 0};
+    int td[4] = {0, 0, 0, 0}, ta[4] = {0, 0, 0, 0}, sh[4] = {1, 1, 1, 1}, sv[4] = {1, 1, 1, 1}, sbo[4] = {0, 0, 0, 0},
+        ldc[4] = {0, 0, 0, 0};
     int c0 = 0;
 #pragma unroll
-    for (int q = 0; q < 3; q++) {
+    for (int q = 0; q < 4; q++) {
       if (q >= ns) break;
       const int cid = s[1 + 2 * q];
       int c = 0;
-      while (c < ncomp && d->comp_id[c] != cid) c++;
+      while (c < ncomp && comp_id_of(*d, c) != cid) c++;
       if (c == ncomp) return SDSJ_CORRUPT;
+      const CompDesc cq = comp_of(*d, c);
       // a component coded a second time: libjpeg overlays the coefficients (and only warns)
       if ((coded >> c) & 1) return SDSJ_UNSUPPORTED;
       coded |= 1 << c;
       if (q == 0) c0 = c;
       td[q] = s[2 + 2 * q] >> 4;
       ta[q] = s[2 + 2 * q] & 15;
-      sh[q] = d->comp[c].h;
-      sv[q] = d->comp[c].v;
-      sbo[q] = c == 0 ? 0 : c == 1 ? boff1 : boff2;
+      sh[q] = cq.h;
+      sv[q] = cq.v;
+      sbo[q] = c == 0 ? 0 : c == 1 ? boff1 : c == 2 ? boff2 : boff3;
       // latch_quant_tables: the component's table at its (only) scan, into the slot k_idct reads (see EOI)
-      const int tq = d->comp[c].tq;
+      const int tq = cq.tq;
       if (!P->qt_defined[tq]) return SDSJ_CORRUPT;
       for (int i = 0; i < 64; i++) t->qt[c][i] = P->qt[tq][i];
       if (td[q] > 3 || !pderive(P, D, td[q], q, lane)) return SDSJ_CORRUPT;
@@ -128,7 +132,7 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
       if (restart_interval) {
         if (restarts_left == 0) {
           if (pprocess_restart(b, &next_num)) return -1;
-          ldc[0] = ldc[1] = ldc[2] = 0;
+          ldc[0] = ldc[1] = ldc[2] = ldc[3] = 0;
           restarts_left = restart_interval;
         }
         restarts_left--;
@@ -137,7 +141,7 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
     };
     if (ns == 1) {
       // jdinput.c per_scan_setup: a single-component scan walks that component's own block grid, an MCU a block
-      const CompDesc& cp = d->comp[c0];
+      const CompDesc cp = comp_of(*d, c0);
       const int cwb = (cp.dw + 7) / 8, chb = (cp.dh + 7) / 8;
       const int ch = sh[0], cv = sv[0], bo = sbo[0], dsl = td[0], asl = 4 + ta[0];
       for (int by = 0; by < chb; by++) {
@@ -157,7 +161,7 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
         if (st < 0) return SDSJ_CORRUPT;
         if (st) continue;
 #pragma unroll
-        for (int q = 0; q < 3; q++) {
+        for (int q = 0; q < 4; q++) {
           if (q >= ns) break;
           const int nb = sh[q] * sv[q];  // (the component's blocks are consecutive in the MCU, rows of h)
           for (int k = 0; k < nb; k++) sblock(b, D, A, P, td[q], 4 + ta[q], q, coef + (m * bpm + sbo[q] + k) * 64, &ldc[q]);
@@ -174,7 +178,8 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
       const int body = b.pos + 2;
       if (m == 0xD9) {
         // k_idct reads each component's latched table from slot c (a component never coded: zero blocks)
-        for (int c = 0; c < ncomp; c++) d->comp[c].tq = c;
+        for (int c = 0; c < ncomp && c < kMaxComp; c++) d->comp[c].tq = c;
+        if (ncomp > kMaxComp) d->comp3.tq = kMaxComp;
         return SDSJ_OK;
       }
       if ((m >= 0xD0 && m <= 0xD7) || m == 0x01) {
@@ -209,7 +214,7 @@ __device__ __forceinline__ int decode_scans(ImgDesc* d, ImgTables* t, const uint
 }  // namespace
 
 // One wave per image; the lookahead tables of the scan's DC and AC tables in LDS, one PLds each (k_prog's struct as it
-// stands: its fourth scan position and interleaved-DC fields are unused here).  The registers allow 5 waves per SIMD,
+// stands: its interleaved-DC fields are unused here; its fourth scan position serves four-component frames).  The registers allow 5 waves per SIMD,
 // 20 per CU; the 8.2 KB of LDS per one-wave workgroup cap a CU's 160 KB at 19.
 constexpr int kScansThreads = 64;
 __global__ void __launch_bounds__(kScansThreads) __attribute__((amdgpu_waves_per_eu(5)))

@@ -2,6 +2,8 @@
 //
 // Stage map (reference behaviour each kernel reproduces, see DESIGN.md for the layout/rooflines):
 //   k_color    upsampling + YCbCr->RGB (or RGB kept) jdsample.c / jdmainct.c / jdcolor.c
+//   k_cmyk     upsampling + YCCK->CMYK + CMYK->RGB  jdsample.c / jdcolor.c ycck_cmyk_convert / Pillow Unpack.c
+//              (four-component images)             "CMYK;I", Convert.c cmyk2rgb
 //   k_coeffs   resampling tables (doubles)        Pillow Resample.c precompute_coeffs
 //   k_hpass    horizontal pass, uint8 out         Pillow ImagingResampleHorizontal_8bpc
 //   k_vpass    vertical pass + hflip + layout/LUT Pillow ImagingResampleVertical_8bpc,
@@ -84,7 +86,8 @@ __global__ void __launch_bounds__(256) k_color(int n, const ImgDesc* __restrict_
  for (int li = blockIdx.y; li < routes[kRtUnfused]; li += gridDim.y) {
   const int img = rl[li];
   const ImgDesc* d = &descs[img];
-  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->fused || d->png) continue;  // (PNG rows: k_png_unfilter)
+  // (PNG rows: k_png_unfilter; four components: k_cmyk)
+  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->fused || d->png || d->ncomp > kMaxComp) continue;
   const int w = d->src_w, h = d->src_y1 - d->src_y0;
   const int64_t total = (int64_t)w * h;
   const uint8_t* planes = scratch + d->off_planes;
@@ -112,6 +115,96 @@ __global__ void __launch_bounds__(256) k_color(int n, const ImgDesc* __restrict_
     o[0] = (uint8_t)R;
     o[1] = (uint8_t)G;
     o[2] = (uint8_t)B;
+  }
+ }
+}
+
+// ------------------------------------------------------------------------------------------
+// k_cmyk: k_color's counterpart for the four-component images of SDSJ_FORMAT_JPEG_CMYK (route kRtScans, ncomp == 4):
+// the RGB rows [src_y0, src_y1) x [src_x0, src_x0 + src_w) at off_rgb, as PIL.Image.open(...).convert("RGB") has
+// them.  Per pixel: the four planes upsampled as jinit_upsampler chooses per component (up_sample; K too); for YCCK
+// (an Adobe marker whose transform is not 0: default_decompress_parms) the first three through jdcolor.c
+// ycck_cmyk_convert -- C, M, Y = 255 - R, G, B of ycc_rgb_convert, K kept --; all four inverted, as Pillow unpacks
+// every four-layer JPEG ("CMYK;I"); then Convert.c cmyk2rgb: nk = 255 - K, out = clip8(nk - MULDIV255(C, nk)).
+// One thread per group of four consecutive pixels of the packed rows: 12 bytes, three aligned 32-bit stores (the
+// rows start 256-aligned); a component stored at full resolution is read 32 bits at a time where the group lies
+// in one row at an aligned column.  The last, partial group stores bytes.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int muldiv255(int a, int b) {
+  const int t = a * b + 128;
+  return ((t >> 8) + t) >> 8;
+}
+
+__device__ __forceinline__ void up_sample4(const uint8_t* P, const CompDesc& c, int x, int y, bool row4, int* o) {
+  if (row4 && c.rh == 1 && c.rv == 1) {  // (x % 4 == 0, pitch % 8 == 0, the plane 256-aligned)
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(P + (int64_t)y * c.pitch + x);
+#pragma unroll
+    for (int k = 0; k < 4; k++) o[k] = (int)((v >> (8 * k)) & 255u);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) o[k] = up_sample(P, c, x + k, y);
+}
+
+__global__ void __launch_bounds__(256) k_cmyk(const ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
+                                              const int32_t* __restrict__ routes, int cap) {
+ const int32_t* rl = route_list(routes, cap, kRtScans);
+ for (int li = blockIdx.y; li < routes[kRtScans]; li += gridDim.y) {
+  const ImgDesc* d = &descs[rl[li]];
+  if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->ncomp != 4) continue;  // (k_scans may have refused it)
+  const int w = d->src_w, h = d->src_y1 - d->src_y0;
+  const int64_t total = (int64_t)w * h, groups = (total + 3) >> 2;
+  const uint8_t* planes = scratch + d->off_planes;
+  uint8_t* rgb = scratch + d->off_rgb;
+  const bool ycck = d->saw_adobe && d->adobe_transform != 0;
+  const CompDesc c0 = d->comp[0], c1 = d->comp[1], c2 = d->comp[2], c3 = comp_of(*d, 3);
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = g * 4;
+    const int yy = (int)(i / w), xx = (int)(i - (int64_t)yy * w);
+    const int x = d->src_x0 + xx, y = d->src_y0 + yy;
+    const bool full = i + 4 <= total, row = xx + 4 <= w;
+    int s[4][4];  // [component][pixel of the group]
+    if (full && row) {
+      const bool row4 = (x & 3) == 0;
+      up_sample4(planes + c0.plane_off, c0, x, y, row4, s[0]);
+      up_sample4(planes + c1.plane_off, c1, x, y, row4, s[1]);
+      up_sample4(planes + c2.plane_off, c2, x, y, row4, s[2]);
+      up_sample4(planes + c3.plane_off, c3, x, y, row4, s[3]);
+    } else {
+      for (int k = 0; k < 4; k++) {
+        const int64_t ik = i + k < total ? i + k : total - 1;  // (a pixel past the end repeats the last; never stored)
+        const int yk = (int)(ik / w), xk = d->src_x0 + (int)(ik - (int64_t)yk * w);
+        s[0][k] = up_sample(planes + c0.plane_off, c0, xk, d->src_y0 + yk);
+        s[1][k] = up_sample(planes + c1.plane_off, c1, xk, d->src_y0 + yk);
+        s[2][k] = up_sample(planes + c2.plane_off, c2, xk, d->src_y0 + yk);
+        s[3][k] = up_sample(planes + c3.plane_off, c3, xk, d->src_y0 + yk);
+      }
+    }
+    uint32_t px[12];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      int C = s[0][k], M = s[1][k], Y = s[2][k];
+      if (ycck) {
+        uint32_t R, G, B;
+        ycc_to_rgb(C, M, Y, &R, &G, &B);
+        C = 255 - (int)R;
+        M = 255 - (int)G;
+        Y = 255 - (int)B;
+      }
+      const int nk = s[3][k];  // 255 - (255 - K): the inverted K, complemented
+      px[3 * k] = clamp255(nk - muldiv255(255 - C, nk));
+      px[3 * k + 1] = clamp255(nk - muldiv255(255 - M, nk));
+      px[3 * k + 2] = clamp255(nk - muldiv255(255 - Y, nk));
+    }
+    uint8_t* o = rgb + i * 3;
+    if (full) {
+      uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+      for (int q = 0; q < 3; q++)
+        o32[q] = px[4 * q] | (px[4 * q + 1] << 8) | (px[4 * q + 2] << 16) | (px[4 * q + 3] << 24);
+    } else {
+      for (int k = 0; k < 12 && i * 3 + k < total * 3; k++) o[k] = (uint8_t)px[k];
+    }
   }
  }
 }
@@ -361,6 +454,13 @@ hipError_t launch_color(int n, const ImgDesc* descs, uint8_t* scratch, const int
                         uint64_t rm) {
   if (!route_on(rm, kRtUnfused)) return hipSuccess;
   hipLaunchKernelGGL(k_color, dim3(64, n < 64 ? n : 64), dim3(256), 0, s, n, descs, scratch, routes, cap);
+  return hipGetLastError();
+}
+hipError_t launch_cmyk(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+                       uint64_t rm, uint64_t hint) {
+  if (!route_on(rm, kRtScans)) return hipSuccess;
+  hipLaunchKernelGGL(k_cmyk, dim3(16, route_grid(hint, kRtScans, n < 256 ? n : 256)), dim3(256), 0, s, descs, scratch, routes,
+                     cap);
   return hipGetLastError();
 }
 hipError_t launch_coeffs(int n, ImgDesc* descs, const sdsj_op& op, uint8_t* scratch, hipStream_t s) {

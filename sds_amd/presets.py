@@ -194,7 +194,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     reaching the parent through HIP IPC); a string = the address of a running service.
 
     ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` /
-    ``"jpeg-scans"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
@@ -222,7 +222,15 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     restart intervals and with tables redefined between the scans.  One wavefront walks a file's scans, as for
     progressive files.  A file whose scans are not plain sequential ones, or code a component twice, still reruns
     on PIL; so do 4:1:1 / RGB-coded multi-scan files unless ``"jpeg-ext"`` is named as well.  Every other JPEG
-    decodes exactly as without the name.  CMYK / YCCK, arithmetic and 12-bit files still rerun on PIL.
+    decodes exactly as without the name.
+    ``"jpeg-cmyk"`` (it includes ``"jpeg"`` too and combines with every other name) takes four-component sequential
+    files: Adobe CMYK (transform 0, or no Adobe marker) and YCCK (any other transform), baseline / extended frames,
+    with the pixels of PIL's ``convert("RGB")`` -- Pillow's own CMYK files at every ``subsampling``, Photoshop-style
+    YCCK (2x2, 1x1, 1x1, 2x2), restart intervals.  Components that arrive in several scans need ``"jpeg-scans"`` as
+    well, sampling ratios of 3 and 4 ``"jpeg-ext"``.  One wavefront walks a file's scan, so the name is for batched
+    use (GpuDecodeBatch): 640x480 files decode at 15k to 73k images/s in batches of 4,096 against 0.35k to 0.58k on
+    the default route, but a single-image call takes 22 to 120 ms against 2 to 3 ms
+    (``profiles/jpeg_cmyk_bench.jsonl``).  Progressive CMYK / YCCK, arithmetic and 12-bit files still rerun on PIL.
     ``"gif"`` (a base format of its own: it stands alone or beside any other name) takes GIF87a / GIF89a files: the
     first frame on the logical screen, as PIL's ``convert("RGB")`` returns it -- local or global colour table, grey
     files, interlaced frames, a frame smaller than the screen, LZW code sizes 2 to 8.  A frame that leaves the screen,
@@ -231,7 +239,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     PNG, so GIF on the GPU is for batched use only (GpuDecodeBatch): 640x480 photos decode at 11.2k images/s in
     batches of 4,096 against 0.45k on the default route, but a single-image call takes 102 ms against 2.4 ms
     (``profiles/gif_bench.jsonl``).
-    In a served worker process (the decode service) PNG, GIF, ``"jpeg-ext"`` and ``"jpeg-scans"`` samples keep the PIL
+    In a served worker process (the decode service) PNG, GIF, ``"jpeg-ext"``, ``"jpeg-scans"`` and ``"jpeg-cmyk"`` samples keep the PIL
     route whatever this says: the service's wire protocol carries no format mask.
     """
 
@@ -281,8 +289,8 @@ class GpuDecodeResizeImageTransform(BaseTransform):
                 st, info = _lib.png_probe(data, mask)  # (under the mask: a "png-ext" file is sized natively)
             elif eng is not None and mask & _lib.FORMAT_GIF and data[:6] in _lib.GIF_SIGNATURES:
                 st, info = _lib.gif_probe(data)
-            elif eng is not None and mask & (_lib.FORMAT_JPEG_EXT | _lib.FORMAT_JPEG_SCANS):
-                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" file is sized natively)
+            elif eng is not None and mask & (_lib.FORMAT_JPEG_EXT | _lib.FORMAT_JPEG_SCANS | _lib.FORMAT_JPEG_CMYK):
+                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" file is sized natively)
             else:
                 st, info = _lib.probe(data)
             if st != _lib.OK or info.width <= 0 or info.height <= 0:  # not a JPEG this path decodes
@@ -575,7 +583,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"png"``, ``"png-ext"``, ``"png-meta"`` or ``"gif"`` to opt in; see
+    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"png"``, ``"png-ext"``, ``"png-meta"`` or ``"gif"`` to opt in; see
     GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
