@@ -12,7 +12,8 @@
 //     an 'L' image repeats it);
 //   * staging offsets of the step's rows come from a small LDS table, not from uniform registers
 //     (keeps the scalar file from spilling);
-//   * the horizontal taps are KT exactly, coefficients in registers, windows read as aligned dwords.
+//   * the horizontal taps are KT or KT - 1 (the live ones), coefficients in registers, windows read as
+//     aligned dwords.
 // plan_image sets ImgDesc::rs_fast = KT and rs_lay for the images these kernels take; k_resample
 // skips them.
 #include <hip/hip_runtime.h>
@@ -56,35 +57,44 @@ struct LdsF {
   int32_t rinfo[kFRows][8];                                  // step row q: byte offsets of its staged rows
 };
 
-// Pillow horizontal pass of one channel at one output column: KT taps from the byte window that
-// starts hsh bytes into dword w[0] (accumulator from 1 << 21, clip8 after >> 22).
-template <int KT>
+// Pillow horizontal pass of one channel at one output column: NT taps from the byte window that
+// starts hsh bytes into dword w[0] (accumulator from 1 << 21, clip8 after >> 22).  NT is the tile's
+// live tap count (rsf_image: KT - 1 wherever the table's last weight is padding), and only the dwords
+// that hsh + NT bytes span are read: four taps are one realigned dword out of two.
+template <int NT>
 __device__ __forceinline__ int htaps(const uint32_t* w, int hsh, const int32_t* cf) {
-  constexpr int ND = (KT + 3 + 3) / 4 + 1;  // dwords covering hsh + KT bytes, + 1 for the realign
+  constexpr int ND = (NT + 3) / 4 + 1;  // dwords the realigned groups read
   uint32_t d[ND];
 #pragma unroll
   for (int i = 0; i < ND; i++) d[i] = w[i];
   int32_t acc = 1 << 21;
 #pragma unroll
-  for (int g = 0; g * 4 < KT; g++) {
+  for (int g = 0; g * 4 < NT; g++) {
     const uint32_t v = __builtin_amdgcn_alignbyte(d[g + 1], d[g], hsh);  // bytes hsh + 4g ..
 #pragma unroll
-    for (int k = 0; k < 4 && g * 4 + k < KT; k++) acc += tap((int32_t)((v >> (8 * k)) & 0xFF), cf[g * 4 + k]);
+    for (int k = 0; k < 4 && g * 4 + k < NT; k++) acc += tap((int32_t)((v >> (8 * k)) & 0xFF), cf[g * 4 + k]);
   }
   return rs_clip8(acc);
+}
+
+// H pass of one step row at one output column: the channels' rows are cs dwords apart (grayscale: one).
+template <int NT, bool GRAY>
+__device__ __forceinline__ uint32_t hrow(const uint32_t* w, int cs, int hsh, const int32_t* cf) {
+  if (GRAY) return (uint32_t)htaps<NT>(w, hsh, cf);
+  const int s0 = htaps<NT>(w, hsh, cf), s1 = htaps<NT>(w + cs, hsh, cf), s2 = htaps<NT>(w + 2 * cs, hsh, cf);
+  return pack3(s0, s1, s2);
 }
 
 // Pillow vertical pass of one output pixel from the ring (KT <= 7: 8 rows of 256 columns), window
 // starting at ring row P: every tap's row is a compile-time offset from the lane's column, so the
 // reads need no address arithmetic (rsf_image picks P = vmin & 7 with a uniform switch).
 template <int KT, int P, bool GRAY>
-__device__ __forceinline__ void vtaps8(const uint32_t* ring, int lane_col, const int32_t* wk, int32_t& v0, int32_t& v1,
-                                       int32_t& v2) {
+__device__ __forceinline__ void vtaps8(const uint32_t* ring, int lane_col, const int32_t* wk, bool full, int32_t& v0,
+                                       int32_t& v1, int32_t& v2) {
   // (the empty asm keeps the column index a value of this block, so each tap's row becomes the
   // read's immediate offset instead of one of 8 addresses held in registers through the loop)
   asm volatile("" : "+v"(lane_col));
-#pragma unroll
-  for (int k = 0; k < KT; k++) {
+  auto vtap = [&](int k) {
     const uint32_t h = ring[lane_col + ((P + k) & 7) * 256];
     const int32_t w = wk[k];
     if (GRAY) {
@@ -94,21 +104,24 @@ __device__ __forceinline__ void vtaps8(const uint32_t* ring, int lane_col, const
       v1 += tap((int32_t)((h >> 8) & 0xFF), w);
       v2 += tap((int32_t)(h >> 16), w);
     }
-  }
+  };
+#pragma unroll
+  for (int k = 0; k < KT - 1; k++) vtap(k);
+  if (full) vtap(KT - 1);  // (uniform: a strip none of whose rows has KT live taps skips the last one)
 }
 
 template <int KT, bool GRAY>
-__device__ __forceinline__ void vtaps8_at(int p, const uint32_t* ring, int lane_col, const int32_t* wk, int32_t& v0,
-                                          int32_t& v1, int32_t& v2) {
+__device__ __forceinline__ void vtaps8_at(int p, const uint32_t* ring, int lane_col, const int32_t* wk, bool full,
+                                          int32_t& v0, int32_t& v1, int32_t& v2) {
   switch (__builtin_amdgcn_readfirstlane(p)) {  // (uniform: scalar compares, no exec masking)
-    case 0: vtaps8<KT, 0, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    case 1: vtaps8<KT, 1, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    case 2: vtaps8<KT, 2, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    case 3: vtaps8<KT, 3, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    case 4: vtaps8<KT, 4, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    case 5: vtaps8<KT, 5, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    case 6: vtaps8<KT, 6, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
-    default: vtaps8<KT, 7, GRAY>(ring, lane_col, wk, v0, v1, v2); break;
+    case 0: vtaps8<KT, 0, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    case 1: vtaps8<KT, 1, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    case 2: vtaps8<KT, 2, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    case 3: vtaps8<KT, 3, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    case 4: vtaps8<KT, 4, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    case 5: vtaps8<KT, 5, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    case 6: vtaps8<KT, 6, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
+    default: vtaps8<KT, 7, GRAY>(ring, lane_col, wk, full, v0, v1, v2); break;
   }
 }
 
@@ -188,6 +201,15 @@ __device__ void rsf_image(int img, int strip, int tz0, int ntz, const ImgDesc* _
   const int pitchY = d->comp[0].pitch, pitchC = LAY == kRsGray ? 0 : d->comp[1].pitch;
   const int ntiles = (ow + tw - 1) / tw;
   const int r_lo = bv[2 * oy0], r_hi = bv[2 * (oy1 - 1)] + bv[2 * (oy1 - 1) + 1];
+  // Live taps.  A Pillow window holds at most ceil(2 x support) taps while KT = 2 ceil(support) + 1, so the
+  // last weight of every KT-tap row of the table is padding, past the row's count -- the VGA crop to
+  // 256 has 2 x support = 3.75: four taps under KT = 5.  Neither pass multiplies by it: when no
+  // row of the strip (here) and no column of the wave's tile (hlow) has KT taps, both run KT - 1.  The
+  // counts come from the bounds tables, so a table with a full window still takes all KT.  Uniform:
+  // every wave looks at all the strip's rows.
+  bool vfull = false;
+  for (int b = lane; b < ((oy1 - oy0 + 63) & ~63); b += 64)
+    vfull = vfull || __ballot(b < oy1 - oy0 && bv[2 * (oy0 + b) + 1] >= KT) != 0;
   // the strip's vertical windows and weights
   for (int i = t; i < (oy1 - oy0) * kVT; i += kFThreads) {
     const int b = i / kVT, k = i % kVT, oy = oy0 + b;
@@ -221,6 +243,7 @@ __device__ void rsf_image(int img, int strip, int tz0, int ntz, const ImgDesc* _
     int32_t cf[KT];
 #pragma unroll
     for (int j = 0; j < KT; j++) cf[j] = active && j < hc ? kh[(int64_t)xx * KT + j] : 0;
+    const bool hlow = __ballot(hc >= KT) == 0;  // no column of the wave has KT live taps
     // H windows: the converted RGB rows, or (grayscale) the staged luma rows themselves
     const uint32_t* hw = LAY == kRsGray ? L.st + (hm >> 2) : reinterpret_cast<const uint32_t*>(&L.rgb[0][0][0]) + (hm >> 2);
     const int hsh = hm & 3;
@@ -524,14 +547,11 @@ __device__ void rsf_image(int img, int strip, int tz0, int ntz, const ImgDesc* _
           // H. KT taps of step row q -> ring slot.  Each channel's window comes in as aligned dwords
           // (unaligned sub-dword LDS reads are slow) and is realigned with v_alignbyte.
           const int r = ra + q;
-          if (LAY == kRsGray) {
-            ring[(r & rmask) * rstride] = (uint32_t)htaps<KT>(hw + q * G::kYDW, hsh, cf);
-          } else {
-            const int s0 = htaps<KT>(hw + q * 3 * (G::kRgbW / 4), hsh, cf);
-            const int s1 = htaps<KT>(hw + (q * 3 + 1) * (G::kRgbW / 4), hsh, cf);
-            const int s2 = htaps<KT>(hw + (q * 3 + 2) * (G::kRgbW / 4), hsh, cf);
-            ring[(r & rmask) * rstride] = pack3(s0, s1, s2);
-          }
+          constexpr bool kGray = LAY == kRsGray;
+          constexpr int kCS = G::kRgbW / 4;
+          const uint32_t* hq = hw + q * (kGray ? G::kYDW : 3 * kCS);
+          const uint32_t hres = hlow ? hrow<KT - 1, kGray>(hq, kCS, hsh, cf) : hrow<KT, kGray>(hq, kCS, hsh, cf);
+          ring[(r & rmask) * rstride] = hres;
           // V. output rows whose window ends at row r
           while (nvend <= r + 1) {
             const int vmin = nvmin, vcnt = nvend - nvmin;
@@ -544,8 +564,9 @@ __device__ void rsf_image(int img, int strip, int tz0, int ntz, const ImgDesc* _
               // all taps unrolled (KT of them, or 8 when ksv > KT): their ring and weight reads issue
               // together (the weights past the window are zero, k_coeffs / the strip table; ring rows
               // past it are finite values)
-              if (ksv <= KT) vtaps8_at<KT, LAY == kRsGray>(vmin & 7, L.ring, t, wk, v0, v1, v2);
-              else vtaps8_at<8, LAY == kRsGray>(vmin & 7, L.ring, t, wk, v0, v1, v2);
+              // (the last one only when a row of the strip has KT live taps: vfull)
+              if (ksv <= KT) vtaps8_at<KT, LAY == kRsGray>(vmin & 7, L.ring, t, wk, vfull, v0, v1, v2);
+              else vtaps8_at<8, LAY == kRsGray>(vmin & 7, L.ring, t, wk, true, v0, v1, v2);
             } else {
               auto vtap = [&](int k) {
                 const uint32_t h = ring[((vmin + k) & rmask) * rstride];
@@ -558,9 +579,12 @@ __device__ void rsf_image(int img, int strip, int tz0, int ntz, const ImgDesc* _
                   v2 += tap((int32_t)(h >> 16), w);
                 }
               };
-              if (ksv <= KT) {
+              if (ksv <= KT && vfull) {
 #pragma unroll
                 for (int k = 0; k < KT; k++) vtap(k);
+              } else if (ksv <= KT) {
+#pragma unroll
+                for (int k = 0; k < KT - 1; k++) vtap(k);
               } else {
                 for (int k = 0; k < vcnt; k++) vtap(k);
               }
