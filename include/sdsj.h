@@ -157,8 +157,21 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * K, included), ratios of 3 and 4 with SDSJ_FORMAT_JPEG_EXT as well; fractional ratios and more than 10 blocks
  * per MCU stay SDSJ_UNSUPPORTED / SDSJ_CORRUPT as before.  One interleaved scan of all four components decodes
  * with this bit alone; components that arrive in several scans need SDSJ_FORMAT_JPEG_SCANS as well and follow
- * its rules.  Restart intervals are supported.  Progressive (SOF2), arithmetic-coded and 12-bit four-component
- * files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: a four-component file reports
+ * its rules.  Restart intervals are supported.  Progressive (SOF2: SDSJ_FORMAT_JPEG_CMYK_PROG), arithmetic-coded
+ * and 12-bit four-component files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: a four-component file
+ * reports SDSJ_UNSUPPORTED on every entry point.
+ *
+ * SDSJ_FORMAT_JPEG_CMYK_PROG (valid only together with SDSJ_FORMAT_JPEG and SDSJ_FORMAT_JPEG_CMYK, SDSJ_EINVAL
+ * otherwise -- 1024, 1025 and 1536 among them; it combines freely with every other bit) accepts progressive
+ * four-component files: 8-bit SOF2 Huffman frames of four components, as Pillow writes a CMYK image with
+ * progressive=True, decoded as libjpeg decodes them -- DC and AC first and refinement scans, the DC ones
+ * interleaved over up to four components, EOB runs, restart intervals, DHT / DQT / DRI between scans, block
+ * smoothing of all four components when the file ends before its last scans.  Colour space, component ids and
+ * sampling factors follow SDSJ_FORMAT_JPEG_CMYK's rules: the Adobe marker chooses CMYK or YCCK, ratios of 1 and 2
+ * with this bit, ratios of 3 and 4 with SDSJ_FORMAT_JPEG_EXT as well, fractional ratios SDSJ_UNSUPPORTED, more
+ * than 10 blocks per MCU SDSJ_CORRUPT.  SDSJ_FORMAT_JPEG_SCANS plays no part (a progressive file always has
+ * several scans), and SDSJ_CTR_PROGRESSIVE counts these files, as every SOF2 file.  Arithmetic-coded and 12-bit
+ * files stay SDSJ_UNSUPPORTED.  Without the bit nothing changes: a progressive four-component file reports
  * SDSJ_UNSUPPORTED on every entry point.
  *
  * SDSJ_FORMAT_GIF is a third base format (valid alone or with any other bit): GIF87a / GIF89a, the first
@@ -182,6 +195,7 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 #define SDSJ_FORMAT_JPEG_SCANS 128
 #define SDSJ_FORMAT_GIF 256 /* (bits 8 and 32 are not formats: SDSJ_EINVAL) */
 #define SDSJ_FORMAT_JPEG_CMYK 512
+#define SDSJ_FORMAT_JPEG_CMYK_PROG 1024
 
 typedef struct sdsj_png_info {
     int32_t width, height;

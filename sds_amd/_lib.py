@@ -43,6 +43,7 @@ FORMAT_JPEG, FORMAT_PNG, FORMAT_PNG_EXT, FORMAT_PNG_META, FORMAT_JPEG_EXT = 1, 2
 FORMAT_JPEG_SCANS = 128
 FORMAT_GIF = 256
 FORMAT_JPEG_CMYK = 512
+FORMAT_JPEG_CMYK_PROG = 1024
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
 # valid only together with PNG, so the name carries both
 # "png-meta": PNG files as converters and editors write them (iCCP, zTXt, iTXt, chunks after the image data);
@@ -53,19 +54,23 @@ FORMAT_JPEG_CMYK = 512
 # jpegtran -scans writes them); likewise valid only together with JPEG, and combinable with "jpeg-ext"
 # "jpeg-cmyk": four-component sequential JPEG (Adobe CMYK and YCCK files); likewise valid only together with JPEG, and
 # combinable with every other name (components in several scans need "jpeg-scans" too, ratios of 3 and 4 "jpeg-ext")
+# "jpeg-cmyk-prog": progressive (SOF2) four-component JPEG, as Pillow writes a CMYK image with progressive=True; the bit is
+# valid only together with JPEG and JPEG_CMYK, so the name carries all three, and combines with every other name
 # "gif": the first frame of a GIF87a / GIF89a file; a base format of its own, valid alone and with every other name
 FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT,
            "png-meta": FORMAT_PNG | FORMAT_PNG_META, "jpeg-ext": FORMAT_JPEG | FORMAT_JPEG_EXT,
            "jpeg-scans": FORMAT_JPEG | FORMAT_JPEG_SCANS, "gif": FORMAT_GIF,
-           "jpeg-cmyk": FORMAT_JPEG | FORMAT_JPEG_CMYK}
+           "jpeg-cmyk": FORMAT_JPEG | FORMAT_JPEG_CMYK,
+           "jpeg-cmyk-prog": FORMAT_JPEG | FORMAT_JPEG_CMYK | FORMAT_JPEG_CMYK_PROG}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 GIF_SIGNATURES = (b"GIF87a", b"GIF89a")
 
 
 def format_mask(formats) -> int:
-    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "png" / "png-ext" /
-    "png-meta" / "gif" (None: JPEG only, the engine's default).  "jpeg-ext", "jpeg-scans" and "jpeg-cmyk" include
-    "jpeg", as "png-ext" and "png-meta" include "png"; "gif" stands alone or beside any of them."""
+    """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" / "png" /
+    "png-ext" / "png-meta" / "gif" (None: JPEG only, the engine's default).  "jpeg-ext", "jpeg-scans" and "jpeg-cmyk"
+    include "jpeg", and "jpeg-cmyk-prog" includes "jpeg-cmyk" (so ("jpeg-cmyk-prog",) is 1537), as "png-ext" and
+    "png-meta" include "png"; "gif" stands alone or beside any of them."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):
@@ -193,7 +198,7 @@ def load() -> ctypes.CDLL:
 
 def probe(jpg: bytes, mask=None) -> tuple[int, SdsjInfo]:
     """``mask``: the SDSJ_FORMAT_* mask the sample will be decoded under (sdsj_probe_formats: with
-    FORMAT_JPEG_EXT the wider JPEG subset is supported, with FORMAT_JPEG_SCANS multi-scan sequential files, with FORMAT_JPEG_CMYK four-component ones); None: the
+    FORMAT_JPEG_EXT the wider JPEG subset is supported, with FORMAT_JPEG_SCANS multi-scan sequential files, with FORMAT_JPEG_CMYK four-component ones, with FORMAT_JPEG_CMYK_PROG progressive ones too); None: the
     default subset (sdsj_probe)."""
     info = SdsjInfo()
     if mask is None:

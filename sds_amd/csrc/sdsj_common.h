@@ -9,7 +9,8 @@
 // unless the engine's mask has SDSJ_FORMAT_JPEG_EXT: setup_geometry; multi-scan sequential files
 // too, unless it has SDSJ_FORMAT_JPEG_SCANS: parse_headers hands their scans to k_scans; and
 // four-component sequential files -- CMYK / YCCK --, unless it has SDSJ_FORMAT_JPEG_CMYK: k_scans
-// decodes those as well, single-scan ones included).
+// decodes those as well, single-scan ones included; and four-component progressive files, unless it has
+// SDSJ_FORMAT_JPEG_CMYK_PROG too: k_prog4 walks their scans).
 #pragma once
 #include <stdint.h>
 
@@ -282,6 +283,8 @@ SDSJ_HD inline CompDesc comp_of(const ImgDesc& d, int c) {
   return o;
 }
 SDSJ_HD inline int comp_id_of(const ImgDesc& d, int c) { return c < kMaxComp ? d.comp_id[c] : d.comp3.id; }
+// A progressive image of four components (SOF2; SDSJ_FORMAT_JPEG_CMYK_PROG): route kRtProg4, ProgTables4 at off_ptab.
+SDSJ_HD inline bool prog4_image(const ImgDesc& d) { return !d.png && d.progressive == 1 && d.ncomp > kMaxComp; }
 SDSJ_HD inline void put_comp(ImgDesc* d, int c, const CompDesc& v) {
   if (c < kMaxComp) {
     d->comp[c] = v;
@@ -333,6 +336,14 @@ struct ProgTables {
   uint16_t qt[4][64];
   int32_t qt_defined[4];
   int32_t latched[kMaxComp];
+};
+// ... of a progressive image of four components (k_prog4, SDSJ_FORMAT_JPEG_CMYK_PROG): what ProgTables and
+// ImgDesc hold per component for three -- the descriptor's size and offsets are pinned --, for the fourth:
+// its latch flag, and its smoothing bits (ImgDesc::sm_bits' [2][10] of one component), which k_prog4_smooth
+// reads from here.  plan_image sizes off_ptab for this struct when the image is one (prog4_image).
+struct ProgTables4 : ProgTables {
+  int32_t latched3;
+  int8_t sm_bits3[2][10];
 };
 
 // One block boundary met by the speculative decode (for early sync detection).
@@ -485,6 +496,7 @@ enum Route : int32_t {
   kRtPng,                         // PNG samples (k_png_inflate, k_png_unfilter); they resample through kRtUnfused
   kRtScans,                       // multi-scan sequential and four-component images (k_scans; ImgDesc::progressive == kScansSequential)
   kRtGif,                         // GIF samples (k_gif_lzw, k_gif_rgb; SDSJ_FORMAT_GIF); they resample through kRtUnfused
+  kRtProg4,                       // progressive images of four components (k_prog4; SDSJ_FORMAT_JPEG_CMYK_PROG)
   kNumRoutes
 };
 constexpr int kRouteSlots = 48;  // counts [0, kNumRoutes), the rest zero
@@ -628,8 +640,10 @@ SDSJ_HD int parse_headers(const Reader& rd, int64_t n, ImgDesc* d, ImgTables* t,
         d->ncomp = rd(s + 5);
         if (d->height == 0 || d->width == 0) return SDSJ_UNSUPPORTED;  // DNL
         if (sl != 6 + 3 * d->ncomp) return SDSJ_CORRUPT;                // get_sof: JERR_BAD_LENGTH
-        // (four components: sequential frames under SDSJ_FORMAT_JPEG_CMYK; k_prog knows three)
-        const bool four = d->ncomp == 4 && m != 0xC2 && (formats & SDSJ_FORMAT_JPEG_CMYK);
+        // (four components: sequential frames under SDSJ_FORMAT_JPEG_CMYK, progressive ones under
+        // SDSJ_FORMAT_JPEG_CMYK_PROG as well -- k_prog knows three, k_prog4 walks those)
+        const bool four = d->ncomp == 4 && (formats & SDSJ_FORMAT_JPEG_CMYK) &&
+                          (m != 0xC2 || (formats & SDSJ_FORMAT_JPEG_CMYK_PROG));
         if (d->ncomp != 1 && d->ncomp != 3 && !four) return SDSJ_UNSUPPORTED;
         d->hmax = d->vmax = 1;
         for (int c = 0; c < d->ncomp; c++) {

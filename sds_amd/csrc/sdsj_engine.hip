@@ -244,6 +244,8 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   SDSJ_HIP(e, launch_prog(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (e->formats & (SDSJ_FORMAT_JPEG_SCANS | SDSJ_FORMAT_JPEG_CMYK))  // (counts under the progressive stage)
     SDSJ_HIP(e, launch_scans(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
+  if (e->formats & SDSJ_FORMAT_JPEG_CMYK_PROG)  // (progressive files of four components: likewise under "prog")
+    SDSJ_HIP(e, launch_prog4(n, ln.descs, ln.tables, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (evs) (void)hipEventRecord((*evs)[kPngEvent].get(), s);
   if (e->formats & SDSJ_FORMAT_GIF)  // (counts under "png_inflate")
     SDSJ_HIP(e, launch_gif(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
@@ -265,7 +267,9 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
   mark(8);
   SDSJ_HIP(e, launch_color(n, ln.descs, e->scratch.get(), ln.routes, cap, s, rm));
   if (e->formats & SDSJ_FORMAT_JPEG_CMYK)  // (... and k_color to k_cmyk)
-    SDSJ_HIP(e, launch_cmyk(n, ln.descs, e->scratch.get(), ln.routes, cap, s, rm, hint));
+    SDSJ_HIP(e, launch_cmyk(kRtScans, n, ln.descs, e->scratch.get(), ln.routes, cap, s, rm, hint));
+  if (e->formats & SDSJ_FORMAT_JPEG_CMYK_PROG)  // (the progressive ones have a list of their own)
+    SDSJ_HIP(e, launch_cmyk(kRtProg4, n, ln.descs, e->scratch.get(), ln.routes, cap, s, rm, hint));
   mark(9);
   SDSJ_HIP(e, launch_coeffs(n, ln.descs, op, e->scratch.get(), s));
   mark(10);
@@ -712,6 +716,7 @@ int sdsj_probe(const uint8_t* jpg, size_t n, sdsj_info* out) { return sdsj_probe
 
 int sdsj_probe_formats(const uint8_t* jpg, size_t n, int formats, sdsj_info* out) {
   if (!jpg || !out || !(formats & SDSJ_FORMAT_JPEG)) return SDSJ_EINVAL;
+  if ((formats & SDSJ_FORMAT_JPEG_CMYK_PROG) && !(formats & SDSJ_FORMAT_JPEG_CMYK)) return SDSJ_EINVAL;  // (valid_formats)
   memset(out, 0, sizeof(*out));
   ImgDesc d;
   static thread_local ImgTables t;
@@ -741,9 +746,12 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 }
 
 // A format mask names at least one of JPEG, PNG and GIF, nothing unknown, PNG_EXT and PNG_META (alone or
-// together) only with PNG, and JPEG_EXT, JPEG_SCANS and JPEG_CMYK (in any combination) only with JPEG.
+// together) only with PNG, JPEG_EXT, JPEG_SCANS and JPEG_CMYK (in any combination) only with JPEG, and JPEG_CMYK_PROG
+// only with JPEG_CMYK (and so with JPEG).
 static bool valid_formats(int mask) {
-  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META, jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS | SDSJ_FORMAT_JPEG_CMYK;
+  const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META;
+  const int jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS | SDSJ_FORMAT_JPEG_CMYK | SDSJ_FORMAT_JPEG_CMYK_PROG;
+  if ((mask & SDSJ_FORMAT_JPEG_CMYK_PROG) && !(mask & SDSJ_FORMAT_JPEG_CMYK)) return false;
   const int base = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_GIF, all = base | sub | jsub;
   return (mask & base) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
          (!(mask & jsub) || (mask & SDSJ_FORMAT_JPEG));

@@ -84,7 +84,7 @@ __device__ __forceinline__ void dequant8(const uint32_t* m, const uint32_t* h, c
 #define SDSJ_IDCT_WAVES 4  // waves per SIMD the register budget targets (124 VGPRs at 4)
 #endif
 // NC: the components the instantiation holds.  k_idct<kMaxComp> is the kernel every mask launches and leaves
-// four-component images alone; k_idct<4> takes only those -- k_scans' images (int16 blocks, no cut restart
+// four-component images alone; k_idct<4> takes only those -- k_scans' and k_prog4's images (int16 blocks, no cut restart
 // intervals), whose fourth component comes from comp_of -- and is launched only under SDSJ_FORMAT_JPEG_CMYK.
 template <int NC>
 __global__ void __launch_bounds__(kIdctThreads) __attribute__((amdgpu_waves_per_eu(SDSJ_IDCT_WAVES)))
@@ -294,7 +294,7 @@ hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uin
 }
 // (grid rows = the lane's images, as for k_idct: a row whose image has not four components exits at once)
 hipError_t launch_idct4(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s, uint64_t rm) {
-  if (!route_on(rm, kRtScans)) return hipSuccess;
+  if (!route_on(rm, kRtScans) && !route_on(rm, kRtProg4)) return hipSuccess;  // (sequential and progressive ones)
   hipLaunchKernelGGL(k_idct<4>, dim3(kIdctGrid, n), dim3(kIdctThreads), 0, s, n, descs, tables, scratch);
   return hipGetLastError();
 }

@@ -63,7 +63,12 @@ hipError_t launch_scanmap(int n, const uint8_t* blob, const int64_t* offsets, Im
 hipError_t launch_prog(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
                        const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                        uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
-// k_prog_zero (sdsj_progressive.hip) over the images of route rt (kRtProg or kRtScans): their int16 coefficient arrays zeroed
+// progressive images of four components (route kRtProg4; engines with SDSJ_FORMAT_JPEG_CMYK_PROG): the same sequence
+// through the four-component instantiations k_prog4, k_prog4_dcs and k_prog4_smooth
+hipError_t launch_prog4(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
+                        const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+                        uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
+// k_prog_zero (sdsj_progressive.hip) over the images of route rt (kRtProg, kRtProg4 or kRtScans): their int16 coefficient arrays zeroed
 void launch_coef_zero(int rt, int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                       uint64_t hint);
 // multi-scan sequential images and four-component ones (route kRtScans; engines with SDSJ_FORMAT_JPEG_SCANS or
@@ -98,11 +103,12 @@ hipError_t launch_entwrite(int n, ImgDesc* descs, const void* etab, uint8_t* scr
                            const HintLane* hl = nullptr);
 hipError_t launch_idct(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s);
 // four-component images (CMYK / YCCK; engines with SDSJ_FORMAT_JPEG_CMYK), which k_idct<kMaxComp> and k_color skip:
-// k_idct<4> (sdsj_idct.hip) over the lane's images, k_cmyk (sdsj_unfused.hip) over route kRtScans' list; both take
-// only the images of four components
+// k_idct<4> (sdsj_idct.hip) over the lane's images, k_cmyk<RT> (sdsj_unfused.hip) over the list of route rt -- kRtScans:
+// the sequential ones, kRtProg4: the progressive ones of SDSJ_FORMAT_JPEG_CMYK_PROG --; both take only the images of
+// four components
 hipError_t launch_idct4(int n, const ImgDesc* descs, const ImgTables* tables, uint8_t* scratch, hipStream_t s,
                         uint64_t rm = kAllRoutes);
-hipError_t launch_cmyk(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+hipError_t launch_cmyk(int rt, int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                        uint64_t rm = kAllRoutes, uint64_t hint = kAllRoutes);
 hipError_t launch_color(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                         uint64_t rm = kAllRoutes);

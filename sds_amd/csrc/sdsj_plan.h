@@ -188,7 +188,8 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
   d->off_tiles = take((int64_t)d->ntiles * sizeof(UsTile));
   d->off_sub = take((int64_t)d->nsub_cap * sizeof(SubState));
   d->off_rec = take((int64_t)d->nsub_cap * kRec * sizeof(SyncRec));
-  d->off_ptab = take(prog ? (int64_t)sizeof(ProgTables) : 0);
+  // (a progressive image of four components: the fourth one's latch flag and smoothing bits follow the tables)
+  d->off_ptab = take(prog ? (int64_t)(prog4_image(*d) ? sizeof(ProgTables4) : sizeof(ProgTables)) : 0);
   d->off_coef = take(coef_bytes(*d, slots));
   int64_t planes = 0;
   for (int c = 0; c < d->ncomp; c++) {
@@ -218,7 +219,7 @@ SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
   }
   const int ns = d.progressive ? 0 : huff_slots(d);  // (it chooses among the baseline entropy routes only)
   *ru = d.progressive ? -1 : (d.ntiles > kUsSerialTiles || d.lat ? kRtUsBig : kRtUsSmall);
-  *re = d.progressive == kScansSequential ? kRtScans : d.progressive ? kRtProg : ns > 4 ? kRtEnt10 : (d.ent_groups > 1 ? kRtEnt11M : kRtEnt11);
+  *re = d.progressive == kScansSequential ? kRtScans : d.progressive ? (prog4_image(d) ? kRtProg4 : kRtProg) : ns > 4 ? kRtEnt10 : (d.ent_groups > 1 ? kRtEnt11M : kRtEnt11);
   *rr = d.geo == kGeoZeros ? -1
         : !d.fused ? kRtUnfused
                    : (d.rs_fast ? rs_route(d.rs_lay, d.rs_fast) : gen_route(d.need_h ? d.ksh : 1));

@@ -142,7 +142,42 @@ __device__ __forceinline__ int prefine(PBits& b, const PLds& P, const ProgTables
   return v;
 }
 
+// What the decoder keeps per component, for NC components.  NC == kMaxComp (k_prog, k_prog_smooth) reads the
+// descriptor's and ProgTables' own arrays and nothing else, so those kernels compile to what they compiled to before
+// the fourth component; NC == 4 (k_prog4, k_prog4_smooth; SDSJ_FORMAT_JPEG_CMYK_PROG) adds the packed fourth component
+// (ImgDesc::comp3) and its state behind the tables (ProgTables4, which off_ptab then holds).
+template <int NC>
+__device__ __forceinline__ int pc_id(const ImgDesc* d, int c) {
+  if constexpr (NC > kMaxComp) return c < kMaxComp ? d->comp_id[c] : d->comp3.id;
+  else return d->comp_id[c];
+}
+#define SDSJ_PC_FIELD(name, f)                                          \
+  template <int NC>                                                     \
+  __device__ __forceinline__ int name(const ImgDesc* d, int c) {        \
+    if constexpr (NC > kMaxComp) return c < kMaxComp ? d->comp[c].f : d->comp3.f; \
+    else return d->comp[c].f;                                           \
+  }
+SDSJ_PC_FIELD(pc_h, h)
+SDSJ_PC_FIELD(pc_v, v)
+SDSJ_PC_FIELD(pc_tq, tq)
+SDSJ_PC_FIELD(pc_bw, bw)
+SDSJ_PC_FIELD(pc_dw, dw)
+SDSJ_PC_FIELD(pc_dh, dh)
+#undef SDSJ_PC_FIELD
+template <int NC>
+__device__ __forceinline__ int32_t* pc_latched(ProgTables* P, int c) {
+  if constexpr (NC > kMaxComp) return c < kMaxComp ? &P->latched[c] : &static_cast<ProgTables4*>(P)->latched3;
+  else return &P->latched[c];
+}
+// coef_bits (s = 0) / prev_coef_bits (s = 1) of component c, coefficients 0..9
+template <int NC>
+__device__ __forceinline__ int8_t* pc_sm(ImgDesc* d, ProgTables* P, int s, int c) {
+  if constexpr (NC > kMaxComp) return c < kMaxComp ? d->sm_bits[s][c] : static_cast<ProgTables4*>(P)->sm_bits3[s];
+  else return d->sm_bits[s][c];
+}
+
 // Every scan of image d, then the markers up to EOI.  Returns an SDSJ status.
+template <int NC>
 __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, const uint8_t* raw, int n, int16_t* coef,
                                   ProgTables* P, PLds& L, int lane) {
   // table state as k_parse left it (the DHT / DQT segments before the first SOS)
@@ -157,20 +192,21 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
       for (int i = 0; i < 256; i++) P->vals[slot][i] = h.vals[i];
     }
   }
-  for (int c = 0; c < kMaxComp; c++) P->latched[c] = 0;
+  for (int c = 0; c < NC; c++) *pc_latched<NC>(P, c) = 0;
   d->t_spec = d->t_sync = d->t_scan = d->t_write = 0;
 #ifdef SDSJ_PROG_STATS
   d->sym_spec = d->sym_sync = d->sym_write = d->it_write = 0;
 #endif
   // block smoothing state (jdphuff.c start_pass_phuff_decoder coef_bits / prev_coef_bits)
   d->smooth = 0;
-  for (int c = 0; c < kMaxComp; c++)
-    for (int k = 0; k < 10; k++) d->sm_bits[0][c][k] = d->sm_bits[1][c][k] = -1;
+  for (int c = 0; c < NC; c++)
+    for (int k = 0; k < 10; k++) pc_sm<NC>(d, P, 0, c)[k] = pc_sm<NC>(d, P, 1, c)[k] = -1;
   int nscans = 0, good = 1 << 30;
   int restart_interval = d->restart_interval;
   // first block of components 1 and 2 within an MCU
   const int boff1 = d->ncomp > 1 ? d->comp[0].h * d->comp[0].v : 0;
   const int boff2 = d->ncomp > 2 ? boff1 + d->comp[1].h * d->comp[1].v : 0;
+  const int boff3 = NC > kMaxComp && d->ncomp > 3 ? boff2 + d->comp[2].h * d->comp[2].v : 0;  // (the fourth one's)
   int pos = (int)d->sos_pos;
   for (;;) {
     if (pos + 2 > n) return SDSJ_CORRUPT;
@@ -187,7 +223,7 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
       if (q >= ns) break;
       const int cid = s[1 + 2 * q];
       int c = 0;
-      while (c < d->ncomp && d->comp_id[c] != cid) c++;
+      while (c < d->ncomp && pc_id<NC>(d, c) != cid) c++;
       if (c == d->ncomp) return SDSJ_CORRUPT;
       comps[q] = c;
       td[q] = s[2 + 2 * q] >> 4;  // checked only where the table is used (jpeg_make_d_derived_tbl)
@@ -203,11 +239,11 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (q >= ns) break;
-      const int c = comps[q], tq = d->comp[c].tq;
-      if (!P->latched[c]) {  // latch_quant_tables: the component's table at its first scan
+      const int c = comps[q], tq = pc_tq<NC>(d, c);
+      if (!*pc_latched<NC>(P, c)) {  // latch_quant_tables: the component's table at its first scan
         if (!P->qt_defined[tq]) return SDSJ_CORRUPT;
         for (int i = 0; i < 64; i++) t->qt[c][i] = P->qt[tq][i];  // (k_idct reads slot c: see below)
-        P->latched[c] = 1;
+        *pc_latched<NC>(P, c) = 1;
       }
       if (ss == 0 && ah == 0) {
         if (td[q] > 3 || !pderive(P, L, td[q], q, lane)) return SDSJ_CORRUPT;
@@ -215,8 +251,8 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
         if (ta[q] > 3 || !pderive(P, L, 4 + ta[q], q, lane)) return SDSJ_CORRUPT;
       }
       // coef_bits of the band (the smoothing reads coefficients 0..9), the previous values kept
-      for (int k = ss < 1 ? ss : 1; k < 10; k++) d->sm_bits[1][c][k] = nscans > 0 ? d->sm_bits[0][c][k] : 0;
-      for (int k = ss; k <= se && k < 10; k++) d->sm_bits[0][c][k] = (int8_t)al;
+      for (int k = ss < 1 ? ss : 1; k < 10; k++) pc_sm<NC>(d, P, 1, c)[k] = nscans > 0 ? pc_sm<NC>(d, P, 0, c)[k] : 0;
+      for (int k = ss; k <= se && k < 10; k++) pc_sm<NC>(d, P, 0, c)[k] = (int8_t)al;
     }
     nscans++;
     good = 1 << 30;
@@ -226,10 +262,11 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       if (q >= ns) break;
-      sh[q] = d->comp[comps[q]].h;
-      sv[q] = d->comp[comps[q]].v;
-      sbw[q] = d->comp[comps[q]].bw;
-      sbo[q] = comps[q] == 0 ? 0 : comps[q] == 1 ? boff1 : boff2;
+      sh[q] = pc_h<NC>(d, comps[q]);
+      sv[q] = pc_v<NC>(d, comps[q]);
+      sbw[q] = pc_bw<NC>(d, comps[q]);
+      if constexpr (NC > kMaxComp) sbo[q] = comps[q] == 0 ? 0 : comps[q] == 1 ? boff1 : comps[q] == 2 ? boff2 : boff3;
+      else sbo[q] = comps[q] == 0 ? 0 : comps[q] == 1 ? boff1 : boff2;
     }
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -243,9 +280,8 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
     // jdinput.c per_scan_setup: a single-component scan walks that component's own block grid
     int nmcu, cwb = 0;
     if (ns == 1) {
-      const CompDesc& cp = d->comp[comps[0]];
-      cwb = (cp.dw + 7) / 8;
-      nmcu = cwb * ((cp.dh + 7) / 8);
+      cwb = (pc_dw<NC>(d, comps[0]) + 7) / 8;
+      nmcu = cwb * ((pc_dh<NC>(d, comps[0]) + 7) / 8);
     } else {
       nmcu = mcux * d->mcuy;
     }
@@ -403,17 +439,22 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
       const int body = b.pos + 2;
       if (m == 0xD9) {
         // k_idct reads each component's latched table from slot c
-        for (int c = 0; c < d->ncomp; c++) d->comp[c].tq = c;
+        if constexpr (NC > kMaxComp) {
+          for (int c = 0; c < d->ncomp && c < kMaxComp; c++) d->comp[c].tq = c;
+          if (d->ncomp > kMaxComp) d->comp3.tq = kMaxComp;
+        } else {
+          for (int c = 0; c < d->ncomp; c++) d->comp[c].tq = c;
+        }
         // jdcoefct.c smoothing_ok: every component's latched Q00..Q30 nonzero and its DC at least
         // partly known; useful when a coefficient 1..9 of some component is not exact
         bool ok = true, useful = false;
         for (int c = 0; c < d->ncomp; c++) {
           const uint16_t* qc = t->qt[c];
           ok = ok && qc[0] && qc[1] && qc[8] && qc[16] && qc[9] && qc[2] && qc[3] && qc[10] && qc[17] && qc[24] &&
-               d->sm_bits[0][c][0] >= 0;
+               pc_sm<NC>(d, P, 0, c)[0] >= 0;
           for (int k = 1; k < 10; k++) {
-            useful = useful || d->sm_bits[0][c][k] != 0;
-            if (nscans <= 1) d->sm_bits[1][c][k] = -1;
+            useful = useful || pc_sm<NC>(d, P, 0, c)[k] != 0;
+            if (nscans <= 1) pc_sm<NC>(d, P, 1, c)[k] = -1;
           }
         }
         d->smooth = ok && useful;
@@ -451,7 +492,7 @@ __device__ __forceinline__ int decode_progressive(ImgDesc* d, ImgTables* t, cons
 
 }  // namespace
 
-// Zeroes the coefficient arrays of the images of route rt: the progressive ones (kRtProg: scans accumulate into them)
+// Zeroes the coefficient arrays of the images of route rt: the progressive ones (kRtProg, kRtProg4: scans accumulate into them)
 // or the multi-scan sequential ones (kRtScans: a scan stores only what it codes).
 __global__ void __launch_bounds__(256) k_prog_zero(const ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
                                                    const int32_t* __restrict__ routes, int cap, int rt) {
@@ -481,6 +522,20 @@ __global__ void __launch_bounds__(256) k_prog_dcs(const ImgDesc* __restrict__ de
     for (int64_t i = (int64_t)blockIdx.y * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.y * 256) dcs[i] = coef[i * 64];
   }
 }
+// ... of route kRtProg4's images (a kernel of its own text: shared through a function template, k_prog_dcs' few
+// instructions came out in another order)
+__global__ void __launch_bounds__(256) k_prog4_dcs(const ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
+                                                   const int32_t* __restrict__ routes, int cap) {
+  const int cnt = routes[kRtProg4];
+  for (int li = blockIdx.x; li < cnt; li += gridDim.x) {
+    const ImgDesc* d = &descs[route_list(routes, cap, kRtProg4)[li]];
+    if (d->status != SDSJ_OK || !d->smooth) continue;
+    const int16_t* coef = reinterpret_cast<const int16_t*>(scratch + d->off_coef);
+    int16_t* dcs = reinterpret_cast<int16_t*>(scratch + d->off_planes);
+    const int64_t nb = d->total_blocks;
+    for (int64_t i = (int64_t)blockIdx.y * 256 + threadIdx.x; i < nb; i += (int64_t)gridDim.y * 256) dcs[i] = coef[i * 64];
+  }
+}
 
 // pred = num / (Q << 8) rounded half away from zero, clamped below 2^Al when Al > 0
 // (jdcoefct.c decompress_smooth_data)
@@ -498,6 +553,9 @@ __device__ __forceinline__ int smooth_pred(int64_t num, int64_t q, int al) {
 // plane area -- libjpeg likewise reads the neighbours unmodified while it smooths a copy of the block.
 // Rows: jdcoefct.c's per-iMCU-row choice (the last iMCU row's real rows only); columns clamped to the
 // component's width in blocks (tests/test_gpu_parity.py: bit-exact against the Pillow-pinned CPU restatement).
+// (NC as for decode_progressive: k_prog4_smooth is the instantiation that knows the fourth component -- K is
+// smoothed like every other component --, over route kRtProg4's list)
+template <int NC>
 __device__ void prog_smooth_image(int img, const ImgDesc* __restrict__ descs, const ImgTables* __restrict__ tables,
                                   uint8_t* __restrict__ scratch);
 __global__ void __launch_bounds__(256) k_prog_smooth(const ImgDesc* __restrict__ descs,
@@ -506,9 +564,18 @@ __global__ void __launch_bounds__(256) k_prog_smooth(const ImgDesc* __restrict__
                                                      int cap) {
   const int cnt = routes[kRtProg];
   for (int li = blockIdx.x; li < cnt; li += gridDim.x)
-    prog_smooth_image(route_list(routes, cap, kRtProg)[li], descs, tables, scratch);
+    prog_smooth_image<kMaxComp>(route_list(routes, cap, kRtProg)[li], descs, tables, scratch);
+}
+__global__ void __launch_bounds__(256) k_prog4_smooth(const ImgDesc* __restrict__ descs,
+                                                      const ImgTables* __restrict__ tables,
+                                                      uint8_t* __restrict__ scratch, const int32_t* __restrict__ routes,
+                                                      int cap) {
+  const int cnt = routes[kRtProg4];
+  for (int li = blockIdx.x; li < cnt; li += gridDim.x)
+    prog_smooth_image<4>(route_list(routes, cap, kRtProg4)[li], descs, tables, scratch);
 }
 
+template <int NC>
 __device__ void prog_smooth_image(int img, const ImgDesc* __restrict__ descs, const ImgTables* __restrict__ tables,
                                   uint8_t* __restrict__ scratch) {
   const ImgDesc* d = &descs[img];
@@ -527,10 +594,11 @@ __device__ void prog_smooth_image(int img, const ImgDesc* __restrict__ descs, co
       const int m = (int)(g / bpm), b = (int)(g - (int64_t)m * bpm);
       c = d->blk_comp[b];
       const int my = m / mcux, mx = m - my * mcux;
-      bx = mx * d->comp[c].h + d->blk_dx[b];
-      by = my * d->comp[c].v + d->blk_dy[b];
+      bx = mx * pc_h<NC>(d, c) + d->blk_dx[b];
+      by = my * pc_v<NC>(d, c) + d->blk_dy[b];
     }
-    const CompDesc& cd = d->comp[c];
+    const CompDesc cd4 = NC > kMaxComp ? comp_of(*d, c) : CompDesc();
+    const CompDesc& cd = NC > kMaxComp ? cd4 : d->comp[c];
     const int h = ncomp == 1 ? 1 : cd.h, v = ncomp == 1 ? 1 : cd.v;
     const int wib = (cd.dw + 7) >> 3, hib = (cd.dh + 7) >> 3;
     if (bx >= wib || by >= hib) continue;  // (padding blocks: never output)
@@ -559,7 +627,13 @@ __device__ void prog_smooth_image(int img, const ImgDesc* __restrict__ descs, co
                                       : ((int64_t)(y / v) * mcux + x / h) * bpm + boff + (y % v) * h + (x % h);
         DC[i][jx] = dcs[gg];
       }
-    const int8_t* cb = d->sm_bits[imcu > d->sm_good ? 1 : 0][c];
+    const int8_t* cb;
+    if constexpr (NC > kMaxComp) {
+      const int sb = imcu > d->sm_good ? 1 : 0;
+      cb = c < kMaxComp ? d->sm_bits[sb][c] : reinterpret_cast<const ProgTables4*>(scratch + d->off_ptab)->sm_bits3[sb];
+    } else {
+      cb = d->sm_bits[imcu > d->sm_good ? 1 : 0][c];
+    }
     bool change_dc = true;
     for (int k = 1; k < 10; k++) change_dc = change_dc && cb[k] == -1;
     const uint16_t* qt = tables[img].qt[c];  // (k_prog: the component's latched table sits in slot c)
@@ -628,9 +702,32 @@ k_prog(ImgDesc* __restrict__ descs, ImgTables* __restrict__ tables, const uint8_
     const int img = lst[li];
     ImgDesc* d = &descs[img];
     if (d->status == SDSJ_OK) {
-      const int st = decode_progressive(d, &tables[img], blob + offsets[img], lengths[img],
+      const int st = decode_progressive<kMaxComp>(d, &tables[img], blob + offsets[img], lengths[img],
                                         reinterpret_cast<int16_t*>(scratch + d->off_coef),
                                         reinterpret_cast<ProgTables*>(scratch + d->off_ptab), lds, threadIdx.x);
+      if (st != SDSJ_OK && threadIdx.x == 0) d->status = st;
+    }
+    __syncthreads();  // LDS reuse by the next entry
+  }
+}
+
+// k_prog's instantiation for four components (SDSJ_FORMAT_JPEG_CMYK_PROG; route kRtProg4): the same walker with the
+// fourth component's geometry, latch and smoothing bits (decode_progressive<4>), a kernel of its own so that k_prog's
+// code generation stays what it is.  Launched only by engines whose mask has the bit.
+__global__ void __launch_bounds__(kProgThreads) __attribute__((amdgpu_waves_per_eu(SDSJ_PROG_WAVES)))
+k_prog4(ImgDesc* __restrict__ descs, ImgTables* __restrict__ tables, const uint8_t* __restrict__ blob,
+        const int64_t* __restrict__ offsets, const int32_t* __restrict__ lengths, uint8_t* __restrict__ scratch,
+        const int32_t* __restrict__ routes, int cap) {
+  __shared__ PLds lds;
+  const int cnt = routes[kRtProg4];
+  const int32_t* lst = route_list(routes, cap, kRtProg4);
+  for (int li = blockIdx.x; li < cnt; li += gridDim.x) {  // (one entry per workgroup at the full grid)
+    const int img = lst[li];
+    ImgDesc* d = &descs[img];
+    if (d->status == SDSJ_OK && d->ncomp == 4) {
+      const int st = decode_progressive<4>(d, &tables[img], blob + offsets[img], lengths[img],
+                                           reinterpret_cast<int16_t*>(scratch + d->off_coef),
+                                           reinterpret_cast<ProgTables*>(scratch + d->off_ptab), lds, threadIdx.x);
       if (st != SDSJ_OK && threadIdx.x == 0) d->status = st;
     }
     __syncthreads();  // LDS reuse by the next entry
@@ -658,6 +755,19 @@ hipError_t launch_prog(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* 
                      offsets, lengths, scratch, routes, cap);
   hipLaunchKernelGGL(k_prog_dcs, dim3(gx, 8), dim3(256), 0, s, descs, scratch, routes, cap);
   hipLaunchKernelGGL(k_prog_smooth, dim3(gx, 8), dim3(256), 0, s, descs, tables, scratch, routes, cap);
+  return hipGetLastError();
+}
+
+hipError_t launch_prog4(int n, ImgDesc* descs, ImgTables* tables, const uint8_t* blob, const int64_t* offsets,
+                        const int32_t* lengths, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+                        uint64_t rm, uint64_t hint) {
+  if (!route_on(rm, kRtProg4)) return hipSuccess;
+  const int gx = helper_grid(n, hint, kRtProg4);
+  launch_coef_zero(kRtProg4, n, descs, scratch, routes, cap, s, hint);
+  hipLaunchKernelGGL(k_prog4, dim3(route_grid(hint, kRtProg4, n)), dim3(kProgThreads), 0, s, descs, tables, blob,
+                     offsets, lengths, scratch, routes, cap);
+  hipLaunchKernelGGL(k_prog4_dcs, dim3(gx, 8), dim3(256), 0, s, descs, scratch, routes, cap);
+  hipLaunchKernelGGL(k_prog4_smooth, dim3(gx, 8), dim3(256), 0, s, descs, tables, scratch, routes, cap);
   return hipGetLastError();
 }
 

@@ -120,7 +120,8 @@ __global__ void __launch_bounds__(256) k_color(int n, const ImgDesc* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// k_cmyk: k_color's counterpart for the four-component images of SDSJ_FORMAT_JPEG_CMYK (route kRtScans, ncomp == 4):
+// k_cmyk<RT>: k_color's counterpart for the four-component images of SDSJ_FORMAT_JPEG_CMYK (ncomp == 4) on route RT's
+// list -- kRtScans: sequential files, kRtProg4: progressive ones (SDSJ_FORMAT_JPEG_CMYK_PROG), the same code over another list:
 // the RGB rows [src_y0, src_y1) x [src_x0, src_x0 + src_w) at off_rgb, as PIL.Image.open(...).convert("RGB") has
 // them.  Per pixel: the four planes upsampled as jinit_upsampler chooses per component (up_sample; K too); for YCCK
 // (an Adobe marker whose transform is not 0: default_decompress_parms) the first three through jdcolor.c
@@ -146,10 +147,11 @@ __device__ __forceinline__ void up_sample4(const uint8_t* P, const CompDesc& c, 
   for (int k = 0; k < 4; k++) o[k] = up_sample(P, c, x + k, y);
 }
 
+template <int RT>
 __global__ void __launch_bounds__(256) k_cmyk(const ImgDesc* __restrict__ descs, uint8_t* __restrict__ scratch,
                                               const int32_t* __restrict__ routes, int cap) {
- const int32_t* rl = route_list(routes, cap, kRtScans);
- for (int li = blockIdx.y; li < routes[kRtScans]; li += gridDim.y) {
+ const int32_t* rl = route_list(routes, cap, RT);
+ for (int li = blockIdx.y; li < routes[RT]; li += gridDim.y) {
   const ImgDesc* d = &descs[rl[li]];
   if (d->status != SDSJ_OK || d->geo == kGeoZeros || d->ncomp != 4) continue;  // (k_scans may have refused it)
   const int w = d->src_w, h = d->src_y1 - d->src_y0;
@@ -456,11 +458,12 @@ hipError_t launch_color(int n, const ImgDesc* descs, uint8_t* scratch, const int
   hipLaunchKernelGGL(k_color, dim3(64, n < 64 ? n : 64), dim3(256), 0, s, n, descs, scratch, routes, cap);
   return hipGetLastError();
 }
-hipError_t launch_cmyk(int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
+hipError_t launch_cmyk(int rt, int n, const ImgDesc* descs, uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s,
                        uint64_t rm, uint64_t hint) {
-  if (!route_on(rm, kRtScans)) return hipSuccess;
-  hipLaunchKernelGGL(k_cmyk, dim3(16, route_grid(hint, kRtScans, n < 256 ? n : 256)), dim3(256), 0, s, descs, scratch, routes,
-                     cap);
+  if (!route_on(rm, rt)) return hipSuccess;
+  const dim3 grid(16, route_grid(hint, rt, n < 256 ? n : 256));
+  if (rt == kRtProg4) hipLaunchKernelGGL(k_cmyk<kRtProg4>, grid, dim3(256), 0, s, descs, scratch, routes, cap);
+  else hipLaunchKernelGGL(k_cmyk<kRtScans>, grid, dim3(256), 0, s, descs, scratch, routes, cap);
   return hipGetLastError();
 }
 hipError_t launch_coeffs(int n, ImgDesc* descs, const sdsj_op& op, uint8_t* scratch, hipStream_t s) {

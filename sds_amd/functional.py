@@ -86,7 +86,7 @@ def sniff_format(data: bytes) -> str:
     if head[:2] == b"\xff\xd8":
         return ("JPEG (a mode this path does not decode: arithmetic, 12-bit, lossless, progressive CMYK / YCCK or "
                 "multi-scan; 4:1:1, 4:1:0 and RGB-coded files decode with \"jpeg-ext\" in gpu_formats, multi-scan "
-                "sequential files with \"jpeg-scans\", sequential CMYK / YCCK files with \"jpeg-cmyk\")")
+                "sequential files with \"jpeg-scans\", sequential CMYK / YCCK files with \"jpeg-cmyk\", progressive ones with \"jpeg-cmyk-prog\")")
     if head[:4] == b"RIFF" and head[8:12] == b"WEBP":
         return "WebP"
     for sig, name in _SIGNATURES:

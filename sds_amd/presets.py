@@ -194,7 +194,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     reaching the parent through HIP IPC); a string = the address of a running service.
 
     ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` /
-    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
@@ -230,7 +230,17 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     well, sampling ratios of 3 and 4 ``"jpeg-ext"``.  One wavefront walks a file's scan, so the name is for batched
     use (GpuDecodeBatch): 640x480 files decode at 15k to 73k images/s in batches of 4,096 against 0.35k to 0.58k on
     the default route, but a single-image call takes 22 to 120 ms against 2 to 3 ms
-    (``profiles/jpeg_cmyk_bench.jsonl``).  Progressive CMYK / YCCK, arithmetic and 12-bit files still rerun on PIL.
+    (``profiles/jpeg_cmyk_bench.jsonl``).  Progressive CMYK / YCCK (without ``"jpeg-cmyk-prog"``), arithmetic and
+    12-bit files still rerun on PIL.
+    ``"jpeg-cmyk-prog"`` (it includes ``"jpeg-cmyk"``, and so ``"jpeg"``, and combines with every other name) takes
+    progressive four-component files as well: what Pillow writes for a CMYK image with ``progressive=True`` (18 scans),
+    their YCCK counterparts, any other script of DC / AC first and refinement scans, restart intervals, and files that
+    end before their last scans (block smoothing of all four components, as libjpeg applies it).  Sampling ratios of 3
+    and 4 need ``"jpeg-ext"`` as well.  One wavefront walks all the scans of a file, so the name is for batched use
+    (GpuDecodeBatch): 640x480 files as Pillow writes them at quality 90 decode at 10k (no subsampling) to 23k
+    (``subsampling=2``) images/s in batches of 4,096 against 0.12k to 0.24k on the default route and 1.7k to 3.5k for
+    PIL on 16 cores, but a single-image call takes 101 to 233 ms against 4 to 9 ms
+    (``profiles/jpeg_cmyk_prog_bench.jsonl``).  Every other file decodes exactly as under ``"jpeg-cmyk"``.
     ``"gif"`` (a base format of its own: it stands alone or beside any other name) takes GIF87a / GIF89a files: the
     first frame on the logical screen, as PIL's ``convert("RGB")`` returns it -- local or global colour table, grey
     files, interlaced frames, a frame smaller than the screen, LZW code sizes 2 to 8.  A frame that leaves the screen,
@@ -239,7 +249,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     PNG, so GIF on the GPU is for batched use only (GpuDecodeBatch): 640x480 photos decode at 11.2k images/s in
     batches of 4,096 against 0.45k on the default route, but a single-image call takes 102 ms against 2.4 ms
     (``profiles/gif_bench.jsonl``).
-    In a served worker process (the decode service) PNG, GIF, ``"jpeg-ext"``, ``"jpeg-scans"`` and ``"jpeg-cmyk"`` samples keep the PIL
+    In a served worker process (the decode service) PNG, GIF, ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"`` and ``"jpeg-cmyk-prog"`` samples keep the PIL
     route whatever this says: the service's wire protocol carries no format mask.
     """
 
@@ -290,7 +300,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
             elif eng is not None and mask & _lib.FORMAT_GIF and data[:6] in _lib.GIF_SIGNATURES:
                 st, info = _lib.gif_probe(data)
             elif eng is not None and mask & (_lib.FORMAT_JPEG_EXT | _lib.FORMAT_JPEG_SCANS | _lib.FORMAT_JPEG_CMYK):
-                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" file is sized natively)
+                st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" file is sized natively)
             else:
                 st, info = _lib.probe(data)
             if st != _lib.OK or info.width <= 0 or info.height <= 0:  # not a JPEG this path decodes
@@ -583,7 +593,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"png"``, ``"png-ext"``, ``"png-meta"`` or ``"gif"`` to opt in; see
+    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"jpeg-cmyk-prog"``, ``"png"``, ``"png-ext"``, ``"png-meta"`` or ``"gif"`` to opt in; see
     GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built

@@ -16,7 +16,12 @@ One JSON line per pool and route, each measured once (marked "single_run"):
   latency    one-image calls through the per-sample transform, native and default route (ms per image)
 
 The native line carries PIL's rate on 16 cores over the pool's files.  The lines are printed and appended to --out
-(default profiles/jpeg_cmyk_bench.jsonl).  `python tools/jpeg_cmyk_bench.py [N] [route ...] [--out FILE]`."""
+(default profiles/jpeg_cmyk_bench.jsonl).  `python tools/jpeg_cmyk_bench.py [N] [route ...] [--out FILE]`.
+
+--prog: the progressive pools of gpu_formats "jpeg-cmyk-prog" instead (k_prog4 walks the 18 scans Pillow writes for a
+CMYK image with progressive=True), the same 8 images at quality 90 without subsampling and with subsampling=2;
+native = formats ("jpeg-cmyk-prog",), the default route as above; --out defaults to
+profiles/jpeg_cmyk_prog_bench.jsonl."""
 import io
 import json
 import os
@@ -27,6 +32,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
 CMYK = ("jpeg", "jpeg-cmyk")
+PROG = ("jpeg-cmyk-prog",)
 
 
 def make_pools(count=8):
@@ -65,10 +71,29 @@ def make_pools(count=8):
     return cmyk, ycck
 
 
+def make_prog_pools(count=8):
+    """(no subsampling, subsampling=2): progressive CMYK files as Pillow writes them, of make_pools' images."""
+    import numpy as np
+    from PIL import Image
+
+    from tests.golden.synth import synth_rgb
+    pools = ([], [])
+    for i in range(count):
+        img = Image.fromarray(synth_rgb(np.random.default_rng(4321 + i), 640, 480)).convert("CMYK")
+        for pool, ss in zip(pools, (0, 2)):
+            b = io.BytesIO()
+            img.save(b, "JPEG", quality=90, progressive=True, subsampling=ss)
+            pool.append(b.getvalue())
+    return pools
+
+
 def main():
     import jpeg_ext_bench as E
     args = sys.argv[1:]
-    out = os.path.join(REPO, "profiles", "jpeg_cmyk_bench.jsonl")
+    prog = "--prog" in args
+    if prog:
+        args.remove("--prog")
+    out = os.path.join(REPO, "profiles", "jpeg_cmyk_prog_bench.jsonl" if prog else "jpeg_cmyk_bench.jsonl")
     if "--out" in args:
         k = args.index("--out")
         out = args[k + 1]
@@ -76,12 +101,18 @@ def main():
     n = int(args[0]) if args else 4096
     routes = args[1:] or ["native", "fallback", "latency"]
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    cmyk, ycck = make_pools()
-    pools = (("CMYK as Pillow writes it (Adobe transform 0, 1x1 sampling)", cmyk),
-             ("YCCK 2x2,1x1,1x1,2x2 (Adobe transform 2)", ycck))
+    if prog:
+        p0, p2 = make_prog_pools()
+        pools = (("progressive CMYK as Pillow writes it (18 scans, quality 90, 1x1 sampling)", p0),
+                 ("progressive CMYK as Pillow writes it (18 scans, quality 90, subsampling=2)", p2))
+    else:
+        cmyk, ycck = make_pools()
+        pools = (("CMYK as Pillow writes it (Adobe transform 0, 1x1 sampling)", cmyk),
+                 ("YCCK 2x2,1x1,1x1,2x2 (Adobe transform 2)", ycck))
+    formats = PROG if prog else CMYK
     for case, pool in pools:
-        run = {"native": lambda: E.native(pool, n, case, CMYK), "fallback": lambda: E.fallback(pool, n, case),
-               "latency": lambda: E.latency(pool, n, case, CMYK)}
+        run = {"native": lambda: E.native(pool, n, case, formats), "fallback": lambda: E.fallback(pool, n, case),
+               "latency": lambda: E.latency(pool, n, case, formats)}
         for r in routes:
             line = run[r]()
             line["single_run"] = True
