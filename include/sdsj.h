@@ -186,7 +186,21 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * SDSJ_UNSUPPORTED; an empty screen or frame, a sub-block past the input, an end code or the end of the
  * data before the last pixel, a code above the next free entry and a first code after a clear that is no
  * literal report SDSJ_CORRUPT (PIL raises on the truncated ones).  Callers rerun both on PIL.  Without the
- * bit nothing changes: a GIF reports SDSJ_UNSUPPORTED. */
+ * bit nothing changes: a GIF reports SDSJ_UNSUPPORTED.
+ *
+ * SDSJ_FORMAT_WEBP is a fourth base format (valid alone or with any other bit): lossless WebP (VP8L, RFC 9649),
+ * giving the pixels of PIL.Image.open(...).convert("RGB"), which drops alpha without compositing -- a bare
+ * RIFF / WEBP / VP8L file, or a VP8X file whose ICCP, EXIF, "XMP " and unknown chunks are skipped and whose
+ * canvas equals the frame; chunks padded to even sizes, bytes after the RIFF size ignored.  The whole codec:
+ * the four transforms (predictor modes 0..15, cross-colour, subtract-green, colour-indexing with 1..256
+ * entries) in any order, each at most once; a colour cache of 1..11 bits; a meta-prefix image; simple and
+ * normal prefix codes; LZ77 with the short distance codes.  Lossy files ("VP8 ", with or without ALPH),
+ * animated ones (the VP8X flag, ANIM, ANMF), a canvas that differs from the frame, a non-zero version and a
+ * main image of more than 256 prefix-code groups report SDSJ_UNSUPPORTED; a RIFF or chunk size past the
+ * input, a reserved VP8X bit, a second image chunk, a repeated transform, an incomplete or over-subscribed
+ * prefix code, a copy that starts before the first pixel or ends past the last, and any read beyond the
+ * chunk's last byte report SDSJ_CORRUPT (PIL raises on them).  Callers rerun both on PIL.  Without the bit
+ * nothing changes: a WebP reports SDSJ_UNSUPPORTED. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
 #define SDSJ_FORMAT_PNG_EXT 4
@@ -196,6 +210,7 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 #define SDSJ_FORMAT_GIF 256 /* (bits 8 and 32 are not formats: SDSJ_EINVAL) */
 #define SDSJ_FORMAT_JPEG_CMYK 512
 #define SDSJ_FORMAT_JPEG_CMYK_PROG 1024
+#define SDSJ_FORMAT_WEBP 4096 /* (bit 2048 is not a format either: SDSJ_EINVAL, alone and beside any other bit) */
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -227,8 +242,21 @@ typedef struct sdsj_gif_info {
  * gives the sample with SDSJ_FORMAT_GIF enabled (the LZW data is the device's to judge). */
 int sdsj_gif_probe(const uint8_t* gif, size_t n, sdsj_gif_info* out);
 
+typedef struct sdsj_webp_info {
+    int32_t width, height; /* the image's size: the VP8L or VP8 frame's, or the VP8X canvas while no frame was met */
+    int32_t has_alpha;     /* the VP8L header's alpha bit or the VP8X alpha flag (convert("RGB") drops alpha) */
+    int32_t lossless;      /* 1: VP8L, 0: VP8 (lossy) or no image chunk */
+    int32_t extended;      /* 1: a VP8X file */
+    int32_t supported;     /* 1 if the MI355X path decodes it (when WebP is enabled) */
+} sdsj_webp_info;
+
+/* Host-side parse of one WebP's container and VP8L header (no GPU needed): the size as soon as it is
+ * readable -- of a lossy file too, which stays SDSJ_UNSUPPORTED --, and the status k_parse gives the sample
+ * with SDSJ_FORMAT_WEBP enabled (the prefix-coded data is the device's to judge). */
+int sdsj_webp_probe(const uint8_t* webp, size_t n, sdsj_webp_info* out);
+
 /* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
- * has SDSJ_FORMAT_PNG and GIF samples when it has SDSJ_FORMAT_GIF (a format outside the mask reports
+ * has SDSJ_FORMAT_PNG, GIF samples when it has SDSJ_FORMAT_GIF and WebP samples when it has SDSJ_FORMAT_WEBP (a format outside the mask reports
  * SDSJ_UNSUPPORTED, need 0).  With
  * SDSJ_FORMAT_JPEG_SCANS a multi-scan sequential file that is refused over its scans (not its header: a scan that
  * is not a sequential one, a component coded twice, fill bytes before a stuffed zero) reports that status together
@@ -240,7 +268,7 @@ int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int 
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out);
 int sdsj_engine_destroy(sdsj_engine* eng);
 
-/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG, PNG and GIF) the engine decodes in batches submitted after the
+/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG, PNG, GIF and WEBP) the engine decodes in batches submitted after the
  * call, on every decode entry point: sdsj_decode_resize_batch, sdsj_decode_resize_batch_device,
  * sdsj_submit_batch, sdsj_submit_files (and so what sdsj_wait_batch reports).  Default: JPEG only. */
 int sdsj_engine_set_formats(sdsj_engine* eng, int mask);

@@ -252,6 +252,7 @@ struct ImgDesc {
   // from the IDAT chain at png_idat_pos, k_png_unfilter / k_png_unfilter_ext write the RGB rows at
   // off_rgb.  Bit depth and interlace travel in png_depth_lace (the struct's size and offsets are pinned).
   // png == 2 (kGifSample): a GIF sample (sdsj_gif.h gif_fill_desc says what each field carries then).
+  // png == 3 (kWebpSample): a WebP sample (sdsj_webp.h webp_fill_desc likewise).
   // png == 0 and ncomp == 4: a CMYK / YCCK JPEG (SDSJ_FORMAT_JPEG_CMYK), whose fourth component is comp3 --
   // read through comp_of / comp_id_of, written through put_comp.
   union {
@@ -497,6 +498,7 @@ enum Route : int32_t {
   kRtScans,                       // multi-scan sequential and four-component images (k_scans; ImgDesc::progressive == kScansSequential)
   kRtGif,                         // GIF samples (k_gif_lzw, k_gif_rgb; SDSJ_FORMAT_GIF); they resample through kRtUnfused
   kRtProg4,                       // progressive images of four components (k_prog4; SDSJ_FORMAT_JPEG_CMYK_PROG)
+  kRtWebp,                        // WebP samples (k_webp_decode, k_webp_inverse, k_webp_rgb; SDSJ_FORMAT_WEBP); they resample through kRtUnfused
   kNumRoutes
 };
 constexpr int kRouteSlots = 48;  // counts [0, kNumRoutes), the rest zero

@@ -36,6 +36,10 @@ hipError_t launch_png(int n, ImgDesc* descs, const uint8_t* blob, const int64_t*
 hipError_t launch_gif(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                       uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
                       uint64_t hint = kAllRoutes);
+// WebP samples (route kRtWebp; engines with SDSJ_FORMAT_WEBP): k_webp_decode, k_webp_inverse, k_webp_rgb (sdsj_webp.hip)
+hipError_t launch_webp(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                       uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
+                       uint64_t hint = kAllRoutes);
 // launch_png's kernels of the wider subset (sdsj_png_ext.hip); g: launch_png's grid
 void launch_png_inflate_ext(unsigned g, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                             uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s);

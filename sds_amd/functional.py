@@ -88,7 +88,7 @@ def sniff_format(data: bytes) -> str:
                 "multi-scan; 4:1:1, 4:1:0 and RGB-coded files decode with \"jpeg-ext\" in gpu_formats, multi-scan "
                 "sequential files with \"jpeg-scans\", sequential CMYK / YCCK files with \"jpeg-cmyk\", progressive ones with \"jpeg-cmyk-prog\")")
     if head[:4] == b"RIFF" and head[8:12] == b"WEBP":
-        return "WebP"
+        return "WebP (lossless files decode on the GPU with \"webp\" in gpu_formats)"
     for sig, name in _SIGNATURES:
         if head.startswith(sig):
             return name

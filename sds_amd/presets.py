@@ -194,7 +194,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     reaching the parent through HIP IPC); a string = the address of a running service.
 
     ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` /
-    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"`` / ``"webp"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
@@ -249,7 +249,12 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     PNG, so GIF on the GPU is for batched use only (GpuDecodeBatch): 640x480 photos decode at 11.2k images/s in
     batches of 4,096 against 0.45k on the default route, but a single-image call takes 102 ms against 2.4 ms
     (``profiles/gif_bench.jsonl``).
-    In a served worker process (the decode service) PNG, GIF, ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"`` and ``"jpeg-cmyk-prog"`` samples keep the PIL
+    ``"webp"`` (a base format of its own as well) takes lossless WebP files (VP8L), bare or in a VP8X container with
+    ICCP / EXIF / XMP chunks, as PIL's ``convert("RGB")`` returns them: every transform, colour cache, meta-prefix image
+    and prefix-code form of the codec.  Lossy and animated files, and every stream the GPU path is not sure about (a
+    truncated chunk, an incomplete prefix code, a copy that leaves the image), still rerun on PIL.  One wavefront
+    decodes a whole image, so WebP on the GPU is for batched use only (GpuDecodeBatch; ``profiles/webp_bench.jsonl``).
+    In a served worker process (the decode service) PNG, GIF, WebP, ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"`` and ``"jpeg-cmyk-prog"`` samples keep the PIL
     route whatever this says: the service's wire protocol carries no format mask.
     """
 
@@ -299,6 +304,8 @@ class GpuDecodeResizeImageTransform(BaseTransform):
                 st, info = _lib.png_probe(data, mask)  # (under the mask: a "png-ext" file is sized natively)
             elif eng is not None and mask & _lib.FORMAT_GIF and data[:6] in _lib.GIF_SIGNATURES:
                 st, info = _lib.gif_probe(data)
+            elif eng is not None and mask & _lib.FORMAT_WEBP and _lib.WEBP_SIGNATURE(data):
+                st, info = _lib.webp_probe(data)
             elif eng is not None and mask & (_lib.FORMAT_JPEG_EXT | _lib.FORMAT_JPEG_SCANS | _lib.FORMAT_JPEG_CMYK):
                 st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" file is sized natively)
             else:
@@ -593,7 +600,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"jpeg-cmyk-prog"``, ``"png"``, ``"png-ext"``, ``"png-meta"`` or ``"gif"`` to opt in; see
+    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"jpeg-cmyk-prog"``, ``"png"``, ``"png-ext"``, ``"png-meta"``, ``"gif"`` or ``"webp"`` to opt in; see
     GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
