@@ -200,7 +200,22 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
  * input, a reserved VP8X bit, a second image chunk, a repeated transform, an incomplete or over-subscribed
  * prefix code, a copy that starts before the first pixel or ends past the last, and any read beyond the
  * chunk's last byte report SDSJ_CORRUPT (PIL raises on them).  Callers rerun both on PIL.  Without the bit
- * nothing changes: a WebP reports SDSJ_UNSUPPORTED. */
+ * nothing changes: a WebP reports SDSJ_UNSUPPORTED.
+ *
+ * SDSJ_FORMAT_TIFF is a fifth base format (valid alone or with any other bit): classic TIFF (II or MM; the first
+ * IFD, wherever it lies), giving the pixels of PIL.Image.open(...).convert("RGB").  Strips only (RowsPerStrip of
+ * any value or absent; StripOffsets / StripByteCounts as SHORTs or LONGs), PlanarConfiguration 1, FillOrder 1,
+ * Orientation 1 or absent, 8 bits per sample: grey (photometric 0, inverted, or 1), palette (3, ColorMap of 3 x 256
+ * SHORTs, the high byte of each), RGB (2), RGB with one extra sample whose ExtraSamples is 0 or 2 and grey (1) with one of kind 2 (dropped),
+ * CMYK (5, through PIL's cmyk2rgb).  Compression 1 (none), 32773 (PackBits), 5 (LZW, MSB first with the early
+ * change) and 8 / 32946 (Deflate, a zlib stream per strip); Predictor 1, or 2 with LZW and Deflate.  BigTIFF,
+ * tiles, planar configuration 2, other sample sizes and formats, associated alpha, several extra samples, every other grey file with an extra sample (PIL has no mode for it), YCbCr /
+ * CIELab / mask photometrics, JPEG / CCITT / other compressions, predictor 3, old-style LZW and orientations 2..8
+ * report SDSJ_UNSUPPORTED; an IFD, a value or a strip past the input, unsorted or duplicate tags, a tag outside the short list checked against libtiff (or one of them with another
+ * type or count), RowsPerStrip of 0x80000000..0xFFFFFFFE, strip arrays
+ * that do not match the rows, a palette file without a ColorMap of 768 entries, and a strip that does not decode to
+ * exactly its rows (or whose Adler-32 is wrong or missing) report SDSJ_CORRUPT.  Callers rerun both on PIL.
+ * Without the bit nothing changes: a TIFF reports SDSJ_UNSUPPORTED. */
 #define SDSJ_FORMAT_JPEG 1
 #define SDSJ_FORMAT_PNG 2
 #define SDSJ_FORMAT_PNG_EXT 4
@@ -211,6 +226,7 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
 #define SDSJ_FORMAT_JPEG_CMYK 512
 #define SDSJ_FORMAT_JPEG_CMYK_PROG 1024
 #define SDSJ_FORMAT_WEBP 4096 /* (bit 2048 is not a format either: SDSJ_EINVAL, alone and beside any other bit) */
+#define SDSJ_FORMAT_TIFF 16384 /* (nor is bit 8192) */
 
 typedef struct sdsj_png_info {
     int32_t width, height;
@@ -255,8 +271,24 @@ typedef struct sdsj_webp_info {
  * with SDSJ_FORMAT_WEBP enabled (the prefix-coded data is the device's to judge). */
 int sdsj_webp_probe(const uint8_t* webp, size_t n, sdsj_webp_info* out);
 
+typedef struct sdsj_tiff_info {
+    int32_t width, height;   /* ImageWidth / ImageLength, as soon as they have been read */
+    int32_t samples;         /* samples per pixel as stored (an extra sample included) */
+    int32_t photometric;     /* 0, 1, 2, 3 or 5 */
+    int32_t codec;           /* 1: none, 2: PackBits, 3: LZW, 4: Deflate */
+    int32_t predictor;       /* 1 or 2 */
+    int32_t rows_per_strip;  /* at most the height */
+    int32_t strips;
+    int32_t supported;       /* 1 if the MI355X path decodes it (when TIFF is enabled) */
+} sdsj_tiff_info;
+
+/* Host-side parse of one TIFF's header, first IFD and strip ranges (no GPU needed): the size as soon as it is
+ * readable, and the status k_parse gives the sample with SDSJ_FORMAT_TIFF enabled (the strips' data is the
+ * device's to judge).  The fields after the size are filled only for a supported file. */
+int sdsj_tiff_probe(const uint8_t* tiff, size_t n, sdsj_tiff_info* out);
+
 /* sdsj_plan_need for an engine whose format mask is `formats`: also sizes PNG samples when the mask
- * has SDSJ_FORMAT_PNG, GIF samples when it has SDSJ_FORMAT_GIF and WebP samples when it has SDSJ_FORMAT_WEBP (a format outside the mask reports
+ * has SDSJ_FORMAT_PNG, GIF samples when it has SDSJ_FORMAT_GIF, WebP samples when it has SDSJ_FORMAT_WEBP and TIFF samples when it has SDSJ_FORMAT_TIFF (a format outside the mask reports
  * SDSJ_UNSUPPORTED, need 0).  With
  * SDSJ_FORMAT_JPEG_SCANS a multi-scan sequential file that is refused over its scans (not its header: a scan that
  * is not a sequential one, a component coded twice, fill bytes before a stuffed zero) reports that status together
@@ -268,7 +300,7 @@ int sdsj_plan_need_formats(const uint8_t* img, size_t n, const sdsj_op* op, int 
 int sdsj_engine_create(int hip_device, const sdsj_cfg* cfg, sdsj_engine** out);
 int sdsj_engine_destroy(sdsj_engine* eng);
 
-/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG, PNG, GIF and WEBP) the engine decodes in batches submitted after the
+/* Sets the formats (SDSJ_FORMAT_* mask, at least one of JPEG, PNG, GIF, WEBP and TIFF) the engine decodes in batches submitted after the
  * call, on every decode entry point: sdsj_decode_resize_batch, sdsj_decode_resize_batch_device,
  * sdsj_submit_batch, sdsj_submit_files (and so what sdsj_wait_batch reports).  Default: JPEG only. */
 int sdsj_engine_set_formats(sdsj_engine* eng, int mask);

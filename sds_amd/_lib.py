@@ -36,7 +36,7 @@ EXPORTS = [
     "sdsj_engine_reserve", "sdsj_plan_need", "sdsj_service_serve", "sdsj_engine_set_formats", "sdsj_png_probe",
     "sdsj_plan_need_formats", "sdsj_png_probe_formats", "sdsj_probe_formats", "sdsj_engine_set_hints",
     "sdsj_engine_clear_hints", "sdsj_engine_hint_counters", "sdsj_hint_counter_name", "sdsj_gif_probe",
-    "sdsj_webp_probe",
+    "sdsj_webp_probe", "sdsj_tiff_probe",
 ]
 NUM_COUNTERS = 11  # SDSJ_NUM_COUNTERS
 NUM_HINT_COUNTERS = 4  # SDSJ_NUM_HINT_COUNTERS (the entry-point store's: sdsj_engine_hint_counters)
@@ -46,6 +46,7 @@ FORMAT_GIF = 256
 FORMAT_JPEG_CMYK = 512
 FORMAT_JPEG_CMYK_PROG = 1024
 FORMAT_WEBP = 4096  # (2048 is no format)
+FORMAT_TIFF = 16384  # (nor is 8192)
 # "png-ext": PNG with the wider subset (Adam7, depths 1 / 2 / 4 / 16, more ancillary chunks); the bit is
 # valid only together with PNG, so the name carries both
 # "png-meta": PNG files as converters and editors write them (iCCP, zTXt, iTXt, chunks after the image data);
@@ -60,9 +61,10 @@ FORMAT_WEBP = 4096  # (2048 is no format)
 # valid only together with JPEG and JPEG_CMYK, so the name carries all three, and combines with every other name
 # "gif": the first frame of a GIF87a / GIF89a file; a base format of its own, valid alone and with every other name
 # "webp": lossless WebP (VP8L, bare or in a VP8X container); a base format of its own as well
+# "tiff": classic TIFF in strips, 8 bits per sample (none / PackBits / LZW / Deflate); a base format of its own too
 FORMATS = {"jpeg": FORMAT_JPEG, "png": FORMAT_PNG, "png-ext": FORMAT_PNG | FORMAT_PNG_EXT,
            "png-meta": FORMAT_PNG | FORMAT_PNG_META, "jpeg-ext": FORMAT_JPEG | FORMAT_JPEG_EXT,
-           "jpeg-scans": FORMAT_JPEG | FORMAT_JPEG_SCANS, "gif": FORMAT_GIF, "webp": FORMAT_WEBP,
+           "jpeg-scans": FORMAT_JPEG | FORMAT_JPEG_SCANS, "gif": FORMAT_GIF, "webp": FORMAT_WEBP, "tiff": FORMAT_TIFF,
            "jpeg-cmyk": FORMAT_JPEG | FORMAT_JPEG_CMYK,
            "jpeg-cmyk-prog": FORMAT_JPEG | FORMAT_JPEG_CMYK | FORMAT_JPEG_CMYK_PROG}
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
@@ -74,11 +76,16 @@ def WEBP_SIGNATURE(data) -> bool:
     return data[:4] == b"RIFF" and data[8:12] == b"WEBP"
 
 
+def TIFF_SIGNATURE(data) -> bool:
+    """II*\0 or MM\0* (classic TIFF; BigTIFF is not sized natively)."""
+    return data[:4] in (b"II*\x00", b"MM\x00*")
+
+
 def format_mask(formats) -> int:
     """SDSJ_FORMAT_* mask of a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" / "png" /
-    "png-ext" / "png-meta" / "gif" / "webp" (None: JPEG only, the engine's default).  "jpeg-ext", "jpeg-scans" and "jpeg-cmyk"
+    "png-ext" / "png-meta" / "gif" / "webp" / "tiff" (None: JPEG only, the engine's default).  "jpeg-ext", "jpeg-scans" and "jpeg-cmyk"
     include "jpeg", and "jpeg-cmyk-prog" includes "jpeg-cmyk" (so ("jpeg-cmyk-prog",) is 1537), as "png-ext" and
-    "png-meta" include "png"; "gif" and "webp" stand alone or beside any of them."""
+    "png-meta" include "png"; "gif", "webp" and "tiff" stand alone or beside any of them."""
     if formats is None:
         return FORMAT_JPEG
     if isinstance(formats, str):
@@ -120,6 +127,12 @@ class SdsjGifInfo(ctypes.Structure):
 class SdsjWebpInfo(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("has_alpha", ctypes.c_int32),
                 ("lossless", ctypes.c_int32), ("extended", ctypes.c_int32), ("supported", ctypes.c_int32)]
+
+
+class SdsjTiffInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("samples", ctypes.c_int32),
+                ("photometric", ctypes.c_int32), ("codec", ctypes.c_int32), ("predictor", ctypes.c_int32),
+                ("rows_per_strip", ctypes.c_int32), ("strips", ctypes.c_int32), ("supported", ctypes.c_int32)]
 
 
 class SdsjCfg(ctypes.Structure):
@@ -200,6 +213,7 @@ def load() -> ctypes.CDLL:
         lib.sdsj_png_probe_formats.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, ctypes.POINTER(SdsjPngInfo)]
         lib.sdsj_gif_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjGifInfo)]
         lib.sdsj_webp_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjWebpInfo)]
+        lib.sdsj_tiff_probe.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjTiffInfo)]
         lib.sdsj_plan_need_formats.argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(SdsjOp), ctypes.c_int,
                                                ctypes.POINTER(i64)]
         for name in EXPORTS:
@@ -246,4 +260,12 @@ def webp_probe(webp: bytes) -> tuple[int, SdsjWebpInfo]:
     sample gets under "webp" before its prefix-coded data is decoded."""
     info = SdsjWebpInfo()
     st = load().sdsj_webp_probe(webp, len(webp), ctypes.byref(info))
+    return st, info
+
+
+def tiff_probe(tiff: bytes) -> tuple[int, SdsjTiffInfo]:
+    """sdsj_tiff_probe: the size, the layout of a supported file, and the status the sample gets under "tiff" before
+    its strips are decoded."""
+    info = SdsjTiffInfo()
+    st = load().sdsj_tiff_probe(tiff, len(tiff), ctypes.byref(info))
     return st, info

@@ -229,7 +229,7 @@ class GpuDecodeBatch:
     ``[B, 1, 3, H, W]``, ``image`` removed, ``framerate`` = 960.0 per sample (float64, as
     default_collate stacks Python floats).
     ``gpu_formats``: the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` / ``"jpeg-scans"`` /
-    ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"`` / ``"webp"``
+    ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"`` / ``"webp"`` / ``"tiff"``
     (default JPEG only; see presets.GpuDecodeResizeImageTransform).  With ``"png"`` a PNG shard no longer
     decodes one sample at a time on a host core; PNG on the GPU is meant for this batched use.  With
     ``"jpeg-ext"`` 4:1:1 / 4:1:0 and RGB-coded JPEGs decode in the batch instead of rerunning on PIL, with

@@ -253,6 +253,9 @@ struct ImgDesc {
   // off_rgb.  Bit depth and interlace travel in png_depth_lace (the struct's size and offsets are pinned).
   // png == 2 (kGifSample): a GIF sample (sdsj_gif.h gif_fill_desc says what each field carries then).
   // png == 3 (kWebpSample): a WebP sample (sdsj_webp.h webp_fill_desc likewise).
+  // png == 4 (kTiffSample): a TIFF sample (sdsj_tiff.h tiff_fill_desc likewise: rows per strip, samples per pixel,
+  // strips, the positions of StripOffsets / StripByteCounts / ColorMap, codec, predictor, photometric, entry types
+  // and byte order all fit these fields; off_png takes the decoded strips, height x width x samples bytes).
   // png == 0 and ncomp == 4: a CMYK / YCCK JPEG (SDSJ_FORMAT_JPEG_CMYK), whose fourth component is comp3 --
   // read through comp_of / comp_id_of, written through put_comp.
   union {
@@ -499,6 +502,7 @@ enum Route : int32_t {
   kRtGif,                         // GIF samples (k_gif_lzw, k_gif_rgb; SDSJ_FORMAT_GIF); they resample through kRtUnfused
   kRtProg4,                       // progressive images of four components (k_prog4; SDSJ_FORMAT_JPEG_CMYK_PROG)
   kRtWebp,                        // WebP samples (k_webp_decode, k_webp_inverse, k_webp_rgb; SDSJ_FORMAT_WEBP); they resample through kRtUnfused
+  kRtTiff,                        // TIFF samples (k_tiff_copy, k_tiff_lzw, k_tiff_inflate, k_tiff_rgb; SDSJ_FORMAT_TIFF); they resample through kRtUnfused
   kNumRoutes
 };
 constexpr int kRouteSlots = 48;  // counts [0, kNumRoutes), the rest zero

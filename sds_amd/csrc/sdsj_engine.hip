@@ -251,6 +251,8 @@ int run_lane(sdsj_engine* e, const Lane& ln, int n, bool small, const uint8_t* d
     SDSJ_HIP(e, launch_gif(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (e->formats & SDSJ_FORMAT_WEBP)  // (likewise under "png_inflate")
     SDSJ_HIP(e, launch_webp(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
+  if (e->formats & SDSJ_FORMAT_TIFF)  // (likewise)
+    SDSJ_HIP(e, launch_tiff(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint));
   if (e->formats & SDSJ_FORMAT_PNG)
     SDSJ_HIP(e, launch_png(n, ln.descs, d_blob, d_offsets, d_lengths, e->scratch.get(), ln.routes, cap, s, rm, hint,
                            evs ? (*evs)[kPngEvent + 1].get() : nullptr, e->formats));
@@ -747,14 +749,14 @@ int sdsj_plan_need(const uint8_t* jpg, size_t n, const sdsj_op* op, int64_t* nee
   return st;
 }
 
-// A format mask names at least one of JPEG, PNG, GIF and WEBP, nothing unknown, PNG_EXT and PNG_META (alone or
+// A format mask names at least one of JPEG, PNG, GIF, WEBP and TIFF, nothing unknown, PNG_EXT and PNG_META (alone or
 // together) only with PNG, JPEG_EXT, JPEG_SCANS and JPEG_CMYK (in any combination) only with JPEG, and JPEG_CMYK_PROG
 // only with JPEG_CMYK (and so with JPEG).
 static bool valid_formats(int mask) {
   const int sub = SDSJ_FORMAT_PNG_EXT | SDSJ_FORMAT_PNG_META;
   const int jsub = SDSJ_FORMAT_JPEG_EXT | SDSJ_FORMAT_JPEG_SCANS | SDSJ_FORMAT_JPEG_CMYK | SDSJ_FORMAT_JPEG_CMYK_PROG;
   if ((mask & SDSJ_FORMAT_JPEG_CMYK_PROG) && !(mask & SDSJ_FORMAT_JPEG_CMYK)) return false;
-  const int base = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_GIF | SDSJ_FORMAT_WEBP, all = base | sub | jsub;
+  const int base = SDSJ_FORMAT_JPEG | SDSJ_FORMAT_PNG | SDSJ_FORMAT_GIF | SDSJ_FORMAT_WEBP | SDSJ_FORMAT_TIFF, all = base | sub | jsub;
   return (mask & base) && !(mask & ~all) && (!(mask & sub) || (mask & SDSJ_FORMAT_PNG)) &&
          (!(mask & jsub) || (mask & SDSJ_FORMAT_JPEG));
 }

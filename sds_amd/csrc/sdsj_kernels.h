@@ -40,6 +40,10 @@ hipError_t launch_gif(int n, ImgDesc* descs, const uint8_t* blob, const int64_t*
 hipError_t launch_webp(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                        uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
                        uint64_t hint = kAllRoutes);
+// TIFF samples (route kRtTiff; engines with SDSJ_FORMAT_TIFF): k_tiff_copy, k_tiff_lzw, k_tiff_inflate, k_tiff_rgb (sdsj_tiff.hip)
+hipError_t launch_tiff(int n, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
+                       uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s, uint64_t rm = kAllRoutes,
+                       uint64_t hint = kAllRoutes);
 // launch_png's kernels of the wider subset (sdsj_png_ext.hip); g: launch_png's grid
 void launch_png_inflate_ext(unsigned g, ImgDesc* descs, const uint8_t* blob, const int64_t* offsets, const int32_t* lengths,
                             uint8_t* scratch, const int32_t* routes, int cap, hipStream_t s);

@@ -9,6 +9,7 @@
 #include "sdsj_common.h"
 #include "sdsj_gif.h"
 #include "sdsj_png.h"
+#include "sdsj_tiff.h"
 #include "sdsj_webp.h"
 
 namespace sdsj {
@@ -212,9 +213,9 @@ SDSJ_HD inline int64_t plan_image(ImgDesc* d, const sdsj_op& op, bool frames = f
 // progressive images), entropy variant by the Huffman tables in use (slots as load_tables counts
 // them), resample variant as plan_image chose it (-1 for an empty crop).
 SDSJ_HD inline void image_routes(const ImgDesc& d, int* ru, int* re, int* rr) {
-  if (d.png) {  // (a PNG, a GIF: kGifSample, or a WebP: kWebpSample)
+  if (d.png) {  // (a PNG, a GIF: kGifSample, a WebP: kWebpSample, or a TIFF: kTiffSample)
     *ru = -1;
-    *re = d.png == kGifSample ? kRtGif : d.png == kWebpSample ? kRtWebp : kRtPng;
+    *re = d.png == kGifSample ? kRtGif : d.png == kWebpSample ? kRtWebp : d.png == kTiffSample ? kRtTiff : kRtPng;
     *rr = d.geo == kGeoZeros ? -1 : kRtUnfused;
     return;
   }
@@ -302,7 +303,7 @@ SDSJ_HD inline bool scan_tables_ok(const ImgDesc& d, const ImgTables& t) {
   return true;
 }
 
-// One sample, from its bytes to its plan: a PNG, a GIF or a WebP (where the engine's formats enable it) is parsed and
+// One sample, from its bytes to its plan: a PNG, a GIF, a WebP or a TIFF (where the engine's formats enable it) is parsed and
 // planned for the unfused passes, everything else is a JPEG or SDSJ_UNSUPPORTED.  Returns the status;
 // *d is planned (d->need, the off_* fields, what image_routes reads) only when it is SDSJ_OK.  Table
 // validation is not part of it: the device's sink defers the table bytes (k_parse validates once all
@@ -330,6 +331,13 @@ SDSJ_HD int plan_sample(const Reader& rd, int64_t n, const sdsj_op& op, bool sma
     WebpHdr wh;
     status = webp_parse(rd, n, &wh);
     webp_fill_desc(d, wh);
+    if (status == SDSJ_OK) plan_image(d, op, false, false, true);
+  } else if ((formats & SDSJ_FORMAT_TIFF) && tiff_signature(rd, n)) {
+    // (planned like a PNG: off_png takes the decoded strips -- png_raw = height x width x samples bytes --,
+    // k_tiff_rgb packs the RGB rows at off_rgb)
+    TiffHdr th;
+    status = tiff_parse(rd, n, &th);
+    tiff_fill_desc(d, th);
     if (status == SDSJ_OK) plan_image(d, op, false, false, true);
   } else if (!(formats & SDSJ_FORMAT_JPEG)) {
     status = SDSJ_UNSUPPORTED;

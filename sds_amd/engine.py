@@ -173,7 +173,7 @@ class JpegEngine:
 
     # -- helpers ---------------------------------------------------------------------------
     def _set_formats(self, formats) -> None:
-        """``formats``: a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" / "png" / "png-ext" / "png-meta" / "gif" / "webp", or None for the default (JPEG only).  The per-process
+        """``formats``: a tuple of "jpeg" / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" / "png" / "png-ext" / "png-meta" / "gif" / "webp" / "tiff", or None for the default (JPEG only).  The per-process
         engine is shared between transforms, so the mask travels with every call: the native mask is
         changed only when this call's differs from the one in force."""
         mask = _lib.format_mask(formats)
@@ -228,7 +228,7 @@ class JpegEngine:
                       formats=None) -> tuple[torch.Tensor, np.ndarray]:
         """Decodes host JPEG bytes (a list of bytes, or an EncodedBatch) into a [n, 3, H, W] (or
         [n, H, W, 3]) device tensor.  ``formats``: the sample formats decoded natively, a tuple of "jpeg"
-        / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" / "png" / "png-ext" / "png-meta" / "gif" / "webp" (None: JPEG only, PNG, GIF and WebP samples report
+        / "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" / "png" / "png-ext" / "png-meta" / "gif" / "webp" / "tiff" (None: JPEG only, PNG, GIF, WebP and TIFF samples report
         UNSUPPORTED); see include/sdsj.h for the PNG subset, what "png-ext" and "png-meta" add to it, and what
         "jpeg-ext" (4:1:1, 4:1:0 and the other upsampling ratios of 3 and 4, RGB-coded files) and "jpeg-scans"
         (multi-scan sequential files) and "jpeg-cmyk" (sequential CMYK / YCCK files; "jpeg-cmyk-prog": progressive ones too) add to the JPEG subset.

@@ -74,9 +74,10 @@ def crop_box(w: int, h: int, out_h: int, out_w: int) -> tuple[int, int, int, int
     return 0, top, w, top + nh
 
 
+_TIFF = "TIFF (8-bit files in strips decode on the GPU with \"tiff\" in gpu_formats)"
 _GIF = "GIF (the first frame decodes on the GPU with \"gif\" in gpu_formats)"
 _SIGNATURES = ((b"\x89PNG\r\n\x1a\n", "PNG"), (b"GIF87a", _GIF), (b"GIF89a", _GIF), (b"BM", "BMP"),
-               (b"II*\x00", "TIFF"), (b"MM\x00*", "TIFF"), (b"\x00\x00\x01\x00", "ICO"), (b"8BPS", "PSD"),
+               (b"II*\x00", _TIFF), (b"MM\x00*", _TIFF), (b"\x00\x00\x01\x00", "ICO"), (b"8BPS", "PSD"),
                (b"\x00\x00\x00\x0cjP  ", "JPEG 2000"), (b"\xff\x4f\xff\x51", "JPEG 2000"))
 
 

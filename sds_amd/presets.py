@@ -194,7 +194,7 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     reaching the parent through HIP IPC); a string = the address of a running service.
 
     ``gpu_formats`` (extension): the sample formats the GPU decodes natively, a tuple of ``"jpeg"`` / ``"jpeg-ext"`` /
-    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"`` / ``"webp"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
+    ``"jpeg-scans"`` / ``"jpeg-cmyk"`` / ``"jpeg-cmyk-prog"`` / ``"png"`` / ``"png-ext"`` / ``"png-meta"`` / ``"gif"`` / ``"webp"`` / ``"tiff"``; default ``("jpeg",)``.  With ``"png"``, non-interlaced 8-bit PNGs (gray, RGB, palette, with
     or without alpha) are inflated and unfiltered on the GPU with the pixels of PIL's ``convert("RGB")``;
     every other PNG, and every stream the GPU path is not sure about, still reruns on PIL, so outputs and
     exceptions are those of the default route.  One wavefront inflates a whole image, so PNG on the GPU
@@ -254,7 +254,12 @@ class GpuDecodeResizeImageTransform(BaseTransform):
     and prefix-code form of the codec.  Lossy and animated files, and every stream the GPU path is not sure about (a
     truncated chunk, an incomplete prefix code, a copy that leaves the image), still rerun on PIL.  One wavefront
     decodes a whole image, so WebP on the GPU is for batched use only (GpuDecodeBatch; ``profiles/webp_bench.jsonl``).
-    In a served worker process (the decode service) PNG, GIF, WebP, ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"`` and ``"jpeg-cmyk-prog"`` samples keep the PIL
+    ``"tiff"`` (a base format of its own too) takes classic TIFF files in strips with 8 bits per sample -- grey, palette,
+    RGB, RGB with an unassociated-alpha or unspecified extra sample and grey with unassociated alpha (dropped), CMYK; uncompressed, PackBits, LZW
+    or Deflate, predictor 1 or 2 -- as PIL's ``convert("RGB")`` returns them.  Tiled, planar, BigTIFF, other depths,
+    associated alpha, YCbCr / JPEG / CCITT files and every strip the GPU path is not sure about still rerun on PIL.
+    One wavefront decodes a strip, so one image feeds several at once (``profiles/tiff_bench.jsonl``).
+    In a served worker process (the decode service) PNG, GIF, WebP, TIFF, ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"`` and ``"jpeg-cmyk-prog"`` samples keep the PIL
     route whatever this says: the service's wire protocol carries no format mask.
     """
 
@@ -306,6 +311,8 @@ class GpuDecodeResizeImageTransform(BaseTransform):
                 st, info = _lib.gif_probe(data)
             elif eng is not None and mask & _lib.FORMAT_WEBP and _lib.WEBP_SIGNATURE(data):
                 st, info = _lib.webp_probe(data)
+            elif eng is not None and mask & _lib.FORMAT_TIFF and _lib.TIFF_SIGNATURE(data):
+                st, info = _lib.tiff_probe(data)
             elif eng is not None and mask & (_lib.FORMAT_JPEG_EXT | _lib.FORMAT_JPEG_SCANS | _lib.FORMAT_JPEG_CMYK):
                 st, info = _lib.probe(data, mask)  # (likewise: a "jpeg-ext" / "jpeg-scans" / "jpeg-cmyk" / "jpeg-cmyk-prog" file is sized natively)
             else:
@@ -600,7 +607,7 @@ def create_standard_image_pipeline(
 ) -> Sequence[SampleTransform]:
     """presets.py:716-744 with the decode/resize/to-tensor/normalise chain fused on the GPU.  ``service``:
     see GpuDecodeResizeImageTransform (the decode service for DataLoader workers); ``gpu_formats``: the
-    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"jpeg-cmyk-prog"``, ``"png"``, ``"png-ext"``, ``"png-meta"``, ``"gif"`` or ``"webp"`` to opt in; see
+    formats decoded natively (add ``"jpeg-ext"``, ``"jpeg-scans"``, ``"jpeg-cmyk"``, ``"jpeg-cmyk-prog"``, ``"png"``, ``"png-ext"``, ``"png-meta"``, ``"gif"``, ``"webp"`` or ``"tiff"`` to opt in; see
     GpuDecodeResizeImageTransform).
 
     Output device: with the default ``service="auto"`` and ``output_device=None`` the process that built
